@@ -2,9 +2,14 @@
 """bench.py — training sequences/sec of the SASRec hot path (BASELINE.json metric) on N MI355X.
 
   python bench.py --gpus 1 --steps 200 --warmup 20
+  python bench.py --gpus 1 --steps 200 --warmup 20 --full   (+ every extra leg: rooflines, throughput mode, deterministic mode,
+                                                           strong scaling, CPU baseline, 1-rank RCCL forms; 15 repeats of the timed region)
+  python bench.py ... --dump-outputs DIR                (+ what the last timed step computed, as DIR/<name>.npy)
   python bench.py --gpus N ...                          (stand-alone: re-executes itself under torch.distributed.run, N ranks)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+
+A plain run (no --full) sets up, warms up, times exactly --steps steps once, writes --dump-outputs and prints the line.
 
 A "step" = one pass of the reference's training iteration (model/basemodel.py:193-199) over one batch of
 B = 256 rows per GPU (configs/basemodel.yaml:2) of synthetic Amazon-toys-shaped data (N = 11 925 items,
@@ -438,21 +443,24 @@ def bench_metamodel(args):
     torch.cuda.synchronize()
     parallel.barrier()
     wall = time.perf_counter() - t0
-    # one outer step alone
-    bv = model._local_batch(loader, perm, 0)
-    bv["neg_item"] = model._neg_sampling(bv)
-    bt = model._local_batch(loader, perm, 1)
-    bt["neg_item"] = model._neg_sampling(bt)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(5):
-        model.hypergrad_step(bv, bt)
-    torch.cuda.synchronize()
-    outer_ms = (time.perf_counter() - t1) / 5 * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, module_outputs(model, loss))
     if world > 1:
         wall = parallel.host_allreduce([wall], "max")[0]
     extra = {}
-    if rank == 0 and fused:
+    if args.full:
+        # one outer step alone
+        bv = model._local_batch(loader, perm, 0)
+        bv["neg_item"] = model._neg_sampling(bv)
+        bt = model._local_batch(loader, perm, 1)
+        bt["neg_item"] = model._neg_sampling(bt)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(5):
+            model.hypergrad_step(bv, bt)
+        torch.cuda.synchronize()
+        extra["outer_step_ms"] = (time.perf_counter() - t1) / 5 * 1e3
+    if args.full and rank == 0 and fused:
         # roofline of the weighted inner step's dominant kernel, measured live: the launches of dr4sr_sasrec_fwd_bwd_weighted re-enqueued
         # one by one on the state the last hyper-gradient probe left in the workspace (batch bt), HIP events on the launch stream
         from dr4sr_amd import _lib
@@ -485,7 +493,7 @@ def bench_metamodel(args):
                                    "inner step every step + hyper-gradient outer step every %d steps, B=%d rows/GPU/step, dropout %.2f"
                                    % (args.interval, B, args.dropout),
                        "global_batch": B * world, "seq_len": 50, "parallelism": "dp%d" % world, "hip_graph": True},
-            "outer_step_ms": outer_ms, "final_loss": float(loss)})
+            "final_loss": float(loss)})
     parallel.shutdown()
 
 
@@ -560,8 +568,10 @@ def bench_cl4srec(args):
         torch.cuda.synchronize()
         wall = time.perf_counter() - t0
         form = "API path replayed as one HIP graph per step" if graph else "API path, eager" 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, module_outputs(model, loss))
     extra = {}
-    if not args.no_kernel_roofline:
+    if args.full and not args.no_kernel_roofline:
         # roofline of the dominant launch, measured live: the launches of the MAIN pass (the batch's SASRec step, one of the step's three
         # encoder passes; the views run the same kernels on 2B shorter rows) re-enqueued one by one on the state a fwd_bwd of one
         # materialised batch leaves in the workspace, HIP events on the launch stream
@@ -590,7 +600,7 @@ def bench_cl4srec(args):
                            % (int(sl.sum()), int(vl.sum()))})
         extra["kernel_us_per_step"]["note"] = "launches of the MAIN pass only (one of three encoder passes per step)"
         extra["roofline"].update({"traffic": None, "traffic_source": None})      # (the committed PMC passes are of the plain SASRec step)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from dr4sr_amd.data.synthetic import make_rows
         extra["cpu_baseline"] = cpu_baseline_leg(make_rows(n_items=model.engine.n_items - 1, seed=2024, dense=args.dense), model.engine.n_items - 1,
                                                  "cl4srec", args.dropout)
@@ -649,6 +659,46 @@ def emit(obj):
     out.flush()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20          # elements kept of an array that would take the dump past DUMP_LIMIT_BYTES
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array a caller of the timed path receives after its last step, as out_dir/<name>.npy (float64 stays float64,
+    everything else float32).  Past DUMP_LIMIT_BYTES in all, an array is cut to a fixed seeded sample of DUMP_SAMPLE elements
+    (<name>.sample_idx.npy holds their flat indices), so that two builds given the same arguments are compared element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        conv[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in conv.values())
+    for name in sorted(conv, key=lambda k: -conv[k].nbytes):
+        a = conv[name]
+        if total > DUMP_LIMIT_BYTES and a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            conv[name] = a.reshape(-1)[idx]
+            conv[name + ".sample_idx"] = idx.astype(np.float64)
+            total += conv[name].nbytes + idx.size * 8 - a.nbytes
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def engine_outputs(eng, loss, n_valid):
+    """the training step's results as a caller of the engine sees them: updated parameters, the last step's mean-loss gradients, loss, n_valid"""
+    arrays = {"loss": np.array([loss], np.float64), "n_valid": np.array([n_valid], np.float64)}
+    arrays.update({"param." + k: v for k, v in eng.views.items()})
+    arrays.update({"grad." + k: v for k, v in eng.normalized_grads().items()})
+    return arrays
+
+
+def module_outputs(model, loss):
+    """the model-API paths (MetaModel, CL4SRec): every floating-point entry of the model's state_dict after the last step, and its loss"""
+    arrays = {"loss": np.array([float(loss)], np.float64)}
+    arrays.update({"state." + k: v for k, v in model.state_dict().items() if torch.is_tensor(v) and v.is_floating_point()})
+    return arrays
+
+
 _CRASH_ARMED = [False]
 
 
@@ -705,8 +755,14 @@ def main():
                          "SASRec: weighted inner steps + one hyper-gradient outer step every --interval steps)")
     ap.add_argument("--embed-dim", type=int, default=64, choices=[64, 128],
                     help="sasrec: 128 = BASELINE configs[3] shape (yelp: N=20034 items, d=128, FFN 128)")
-    ap.add_argument("--repeats", type=int, default=15,
-                    help="repetitions of the timed region (each exactly --steps steps): ms_per_step = median, ms_per_step_spread = min / max")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="repetitions of the timed region (each exactly --steps steps): ms_per_step = median, ms_per_step_spread = min / max "
+                         "(default 1; 15 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="every extra leg besides the headline: per-kernel rooflines and microbenches, throughput mode, deterministic mode, "
+                         "strong scaling, CPU baseline, 1-rank RCCL forms (MetaModel: outer step; CL4SRec: kernel roofline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (parameters, gradients, loss) as DIR/<name>.npy")
     ap.add_argument("--in-graph-timeout", type=int, default=150,
                     help="data parallel: seconds the in-graph-collective attempt (second form) may take before the line is printed without it")
     ap.add_argument("--comm-init-timeout", type=float, default=240.0,
@@ -720,6 +776,8 @@ def main():
                     help="whole-run watchdog: after this many seconds the process sends itself SIGTERM — rank 0 then prints the line as "
                          "completed so far (arm_crash_line) instead of hanging the launcher in a wedged collective")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 15 if args.full else 1
     if args.max_seconds > 0:
         import signal
         import threading
@@ -768,11 +826,11 @@ def main():
             _REAL_STDOUT.flush()
             os.abort()
 
-    def measure(B_arg, steps, warmup, extras, dp=dp, dp_form="host", repeats=None, dp_flat=False, deterministic=False):
+    def measure(B_arg, steps, warmup, extras, dp=dp, dp_form="host", repeats=None, dp_flat=False, deterministic=False, dump_dir=None):
         if deterministic:                          # fixed summation order (train.deterministic): the library reads the switch when a plan is carved
             _lib.set_env("DR4SR_DETERMINISTIC", "1")
             try:
-                return measure(B_arg, steps, warmup, extras, dp=dp, dp_form=dp_form, repeats=repeats, dp_flat=dp_flat)
+                return measure(B_arg, steps, warmup, extras, dp=dp, dp_form=dp_form, repeats=repeats, dp_flat=dp_flat, dump_dir=dump_dir)
             finally:
                 _lib.set_env("DR4SR_DETERMINISTIC", None)
         import gc
@@ -1003,6 +1061,8 @@ def main():
             spread = {"repeats": repeats, "median": 1e3 * wall / steps, "min": 1e3 * min(walls) / steps, "max": 1e3 * max(walls) / steps}
             per_rank_ms, coll_us = None, None
             loss, nvalid = eng.loss_and_count()             # (before the stand-alone collective timing below overwrites the gradient tail)
+            if dump_dir and rank == 0:
+                dump_outputs(dump_dir, engine_outputs(eng, loss, nvalid))
             if dp:
                 # this rank's own GPU time per step (events), gathered over the control plane
                 per_rank_ms = [round(x, 5) for x in parallel.host_allgather(gpu_ms / steps)]
@@ -1148,7 +1208,8 @@ def main():
 
         return out, rows_np, N
 
-    out, rows_np, N = measure(args.batch, args.steps, args.warmup, "full")
+    # a plain run stops at the headline (its line, and --dump-outputs); every other leg below runs under --full only
+    out, rows_np, N = measure(args.batch, args.steps, args.warmup, "full" if args.full else None, dump_dir=args.dump_outputs)
     if dp:
         out["collective_forms"] = {"host": out["ms_per_step"], "in_graph": None}
         if parallel.FALLBACK_REASON:
@@ -1156,7 +1217,7 @@ def main():
     arm_crash_line(out, "throughput_mode")                   # from here on the line cannot be lost (see arm_crash_line)
     tm = None
     sec_rep = max(1, min(args.repeats, 5))                   # the secondary sizes: fewer repetitions of a longer timed region
-    if args.model == "sasrec" and args.batch < 8192 and not args.no_throughput_mode:
+    if args.full and args.model == "sasrec" and args.batch < 8192 and not args.no_throughput_mode:
         # BASELINE.md §3 asks for B=256 (reference batch size) AND B=8192 (throughput / scaling mode); same data, same step.
         # Under a multi-rank launch this run is the single-GPU step on every rank (no collective): the 1-GPU reference of `strong`.
         tm, _, _ = measure(8192, max(20, min(100, args.steps)), 10, "kernels" if world == 1 else None, dp=False, repeats=sec_rep)
@@ -1165,7 +1226,7 @@ def main():
                                                           "roofline", "roofline_gather_step", "kernel_us_per_step", "valid_tokens_last_step",
                                                           "roofline_step", "roofline_tile_kernels") if k in tm}
     arm_crash_line(out, "deterministic_mode")
-    if args.model in ("sasrec", "fmlp", "gru4rec") and not dp and rank == 0 and not args.no_deterministic_leg:
+    if args.full and args.model in ("sasrec", "fmlp", "gru4rec") and not dp and rank == 0 and not args.no_deterministic_leg:
         # what run-to-run determinism costs at this workload (train.deterministic; the reference sets cudnn.deterministic, utils/utils.py:19):
         # the same step with every reduction in a fixed order — at-scale launch forms + ordered partial sums in the weight-gradient launch
         try:
@@ -1177,7 +1238,7 @@ def main():
             out["deterministic_mode"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
     arm_crash_line(out, "strong")
     strong = []
-    if args.model == "sasrec" and not args.no_strong and args.embed_dim == 64 and not args.dense and args.batch < 8192:
+    if args.full and args.model == "sasrec" and not args.no_strong and args.embed_dim == 64 and not args.dense and args.batch < 8192:
         # STRONG scaling (north_star: ">= 6x at 8 GPUs"): a FIXED global batch G split over the N ranks (G / N rows per rank per
         # step), one all-reduce per step; `single_gpu_value` = the same G on ONE GPU measured in this very run (every rank runs it
         # as an independent replica, rank 0's number is taken), so speedup and efficiency need no second invocation.
@@ -1203,7 +1264,7 @@ def main():
         if rank == 0:
             out["strong"] = strong
     arm_crash_line(out, "cpu_baseline")
-    if rank == 0 and not dp and not args.no_cpu_baseline and args.model in ("sasrec", "gru4rec", "fmlp"):
+    if args.full and rank == 0 and not dp and not args.no_cpu_baseline and args.model in ("sasrec", "gru4rec", "fmlp"):
         out["cpu_baseline"] = cpu_baseline_leg(rows_np, N, args.model, 0.2 if args.model == "gru4rec" else args.dropout)
 
     # ---- single GPU: what the DATA-PARALLEL form of the step costs beyond the single-GPU step, measured with the one RCCL rank a 1-GPU

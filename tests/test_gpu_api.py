@@ -317,7 +317,7 @@ def test_bench_self_launches_n_ranks_on_a_shared_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-                          "--no-throughput-mode", "--strong-global-batch", "512"], capture_output=True, text=True, timeout=600,
+                          "--no-throughput-mode", "--strong-global-batch", "512", "--full"], capture_output=True, text=True, timeout=600,
                          env=dict(os.environ, DR4SR_BENCH_SHARE_GPU="1"), cwd=root)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, "rc=%s\n" % out.returncode + out.stdout[-3000:] + out.stderr[-6000:]

@@ -206,7 +206,7 @@ def test_bench_self_launches_eight_ranks_on_a_shared_gpu():
     """`python bench.py --gpus 8` (the driver's widest command) on ONE GPU over gloo: every rank takes the data-parallel step, the
     strong-scaling entry splits 16 384 rows into 2 048 per rank; one JSON line from rank 0"""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "4", "--warmup", "2", "--repeats", "2",
-                          "--no-throughput-mode", "--strong-global-batch", "16384"], capture_output=True, text=True, timeout=900,
+                          "--no-throughput-mode", "--strong-global-batch", "16384", "--full"], capture_output=True, text=True, timeout=900,
                          env=dict(os.environ, DR4SR_BENCH_SHARE_GPU="1", DR4SR_DP_BACKEND="gloo"), cwd=ROOT)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stdout[-2000:] + out.stderr[-2000:]

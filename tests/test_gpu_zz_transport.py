@@ -49,7 +49,7 @@ def _one_line(out):
 def test_bench_line_survives_an_abort_in_a_later_leg():
     """single process: SIGABRT at the start of the first extra leg — the headline measurement is complete, the line must appear, marked"""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--repeats", "3", "--no-cpu-baseline",
-                          "--no-strong"], capture_output=True, text=True, timeout=600,
+                          "--no-strong", "--full"], capture_output=True, text=True, timeout=600,
                          env=dict(os.environ, DR4SR_BENCH_INJECT_ABORT="throughput_mode"), cwd=ROOT)
     j = _one_line(out)
     assert out.returncode == 0, report(out)
@@ -128,3 +128,29 @@ def test_a_wedged_communicator_bootstrap_costs_the_timeout_not_the_run(monkeypat
         parallel.shutdown()
         parallel.FALLBACK_REASON = None
         time.sleep(3.0)                                        # let the helper thread's sleep end before the next test
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """a plain run (no --full): exactly --steps timed steps, the headline keys only, and --dump-outputs of the last step; two runs with
+    the same arguments start from identical inputs, so in deterministic mode their outputs are bit-identical"""
+    import numpy as np
+    dumps = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                              "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600,
+                             env=dict(os.environ, DR4SR_DETERMINISTIC="1"), cwd=ROOT)
+        j = _one_line(out)
+        assert out.returncode == 0, report(out)
+        assert j["steps"] == 7 and j["warmup"] == 3 and j["ms_per_step_spread"]["repeats"] == 1 and j["ms_per_step"] > 0
+        assert j["value"] > 0 and j["unit"] == "sequences/s" and j["higher_is_better"] is True and j["dtype"].startswith("f32")
+        assert not {"roofline", "throughput_mode", "deterministic_mode", "strong", "cpu_baseline"} & set(j), sorted(j)
+        files = sorted(os.listdir(tmp_path / d))
+        arrays = {f[:-4]: np.load(tmp_path / d / f) for f in files}
+        assert "loss" in arrays and "param.item_embedding.weight" in arrays and "grad.item_embedding.weight" in arrays
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 64 << 20
+        assert abs(float(arrays["loss"][0]) - j["final_loss"]) < 1e-6
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k

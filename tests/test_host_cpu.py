@@ -609,3 +609,26 @@ def test_control_plane_helpers_gloo_world3():
     assert mx == [2.0, 10.0] and sm == [3.0] and ga == [100.0, 101.0, 102.0]
     assert t == [18.0] * 5                                  # 1 + 2 + 3 = 6 on every rank, then the begin / end form reduces that again: 18
     assert g == [[0, 0], [1, 2], [2, 4]] and b == [1.0]
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one DIR/<name>.npy per array, float32 (float64 kept); past the 64 MB budget an array is cut to a seeded
+    sample whose flat indices are stored beside it — the same sample on every run"""
+    sys.path.insert(0, ROOT)
+    import bench
+    small = {"loss": np.array([0.5], np.float64), "n_valid": np.array([7], np.int64), "param.w": torch.arange(12, dtype=torch.float32).view(3, 4)}
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"loss", "n_valid", "param.w"}
+    assert got["loss"].dtype == np.float64 and got["n_valid"].dtype == np.float32 and got["param.w"].dtype == np.float32
+    np.testing.assert_array_equal(got["param.w"], np.arange(12, dtype=np.float32).reshape(3, 4))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    big = np.random.default_rng(1).standard_normal(5000).astype(np.float32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "loss": np.array([1.0])})
+    idx = np.load(tmp_path / "b" / "big.sample_idx.npy").astype(np.int64)
+    vals = np.load(tmp_path / "b" / "big.npy")
+    assert vals.shape == (100,) and np.array_equal(vals, big[idx]) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "big.sample_idx.npy").astype(np.int64))
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) < 4096

@@ -1,5 +1,5 @@
 """Data-parallel check with REAL RCCL ranks, one device per rank (a multi-GPU node, or the logical devices of one MI355X in DPX / QPX / CPX
-compute-partition mode — tools/partition_rccl_check.sh): W ranks each take a contiguous slice of every global batch, sum-all-reduce the
+compute-partition mode, set up beforehand): W ranks each take a contiguous slice of every global batch, sum-all-reduce the
 flat un-normalised gradient (+ {n_valid, loss} tail) over RCCL and run the same dense Adam step,
   form "host":     the collective launched by the host between backward and optimizer (BaseModel's default),
   form "in_graph": k whole steps (fwd_bwd -> all-reduce -> adam) captured in ONE HIP graph and replayed (train.dp_graph_allreduce);
