@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DR4SR_LIB_PATH") or os.path.join(_HERE, "csrc", "libdr4sr_hip.so")     # override: A/B runs of two builds on one box
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 COMM_ID_BYTES = 128           # DR4SR_COMM_ID_BYTES (the RCCL unique id, a host buffer)
 GRAD_TAIL = 4
 STATE_WORDS = 16
@@ -151,9 +151,24 @@ class GruPlan(C.Structure):
     ]
 
 
+class RegenPlan(C.Structure):
+    """mirror of `dr4sr_regen_plan` (include/dr4sr_hip.h, ABI 9)"""
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("n_rows", C.c_int32), ("K", C.c_int32), ("max_len", C.c_int32),
+        ("D", C.c_int32), ("H", C.c_int32), ("F", C.c_int32), ("n_layer", C.c_int32),
+        ("ln_eps", C.c_float),
+        ("params", _f32p),
+        ("n_params", C.c_int64),
+    ]
+
+
+REGEN_TENSORS = 70            # DR4SR_REGEN_TENSORS
+
 _PLANP = C.POINTER(SasrecPlan)
 _FPLANP = C.POINTER(FmlpPlan)
 _GPLANP = C.POINTER(GruPlan)
+_RPLANP = C.POINTER(RegenPlan)
 
 # name -> (restype, argtypes); every symbol include/dr4sr_hip.h and include/dr4sr_hip_hooks.h (test / measurement hooks) declare
 SYMBOLS = {
@@ -269,6 +284,13 @@ SYMBOLS = {
     "dr4sr_comm_join": (C.c_int, [C.c_void_p, C.c_void_p]),
     "dr4sr_allgather_bytes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "dr4sr_broadcast_bytes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    # ABI 9: dataset regeneration (csrc/regen.hip)
+    "dr4sr_regen_plan_sizeof": (C.c_int, []),
+    "dr4sr_regen_param_layout": (C.c_int64, [C.c_int32, C.c_int32, C.c_void_p]),
+    "dr4sr_regen_workspace_bytes": (C.c_int64, [_RPLANP, C.c_int64, C.c_int32]),
+    "dr4sr_regen_encode": (C.c_int, [_RPLANP, _i64p, _i64p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "dr4sr_regen_decode": (C.c_int, [_RPLANP, _i64p, _i64p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _i64p,
+                                     C.c_void_p, C.c_void_p]),
     "dr4sr_crash_line_set": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32]),           # measurement hook (include/dr4sr_hip_hooks.h)
 }
 
@@ -302,6 +324,8 @@ def load():
         raise Dr4srError("ctypes mirror of dr4sr_fmlp_plan does not match the compiled struct")
     if lib.dr4sr_gru4rec_plan_sizeof() != C.sizeof(GruPlan):
         raise Dr4srError("ctypes mirror of dr4sr_gru4rec_plan does not match the compiled struct")
+    if lib.dr4sr_regen_plan_sizeof() != C.sizeof(RegenPlan):
+        raise Dr4srError("ctypes mirror of dr4sr_regen_plan does not match the compiled struct")
     _lib = lib
     return lib
 

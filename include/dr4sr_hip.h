@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define DR4SR_ABI_VERSION 8
+#define DR4SR_ABI_VERSION 9
 
 #define DR4SR_E_ARG      (-1)   /* null pointer / bad size                                   */
 #define DR4SR_E_SHAPE    (-2)   /* unsupported D / H / F / L combination     */
@@ -578,6 +578,60 @@ int dr4sr_infonce_fwd(const float* xi, const float* xj, const uint8_t* valid, in
                       float* loss_row, float* stats, void* stream);
 int dr4sr_infonce_bwd(const float* xi, const float* xj, const uint8_t* valid, int32_t B, int32_t D, float temperature,
                       const float* lse, const float* scale, float* dxi, float* dxj, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABI 9 — dataset regeneration (stage 3 of DR4SR, the reference's 3.Hybrid_inference.py): greedy decode of every training sequence
+ * under each condition of the pre-trained regenerator (csrc/regen.hip).  The model is nn.Transformer(d_model 64, nhead 2, 2 encoder +
+ * 2 decoder post-norm layers, FFN 256, erf-GELU, layer_norm_eps) with the final encoder / decoder norms, in eval mode:
+ *   encode  : x = E[src] + P[0:Ls] -> 2 bidirectional layers (key padding beyond src_len) -> encoder.norm -> condition_linear[0] + ReLU;
+ *             memory_k = features k*64:(k+1)*64 of condition_linear[2]; both decoder layers' cross-attention K | V of memory_k
+ *   decode  : ys = [SOS]; per step i < max_len - 1: causal self-attention (per-layer K/V cache), cross-attention over memory_k, FFN,
+ *             decoder.norm; logits = h @ E^T over ALL n_rows rows (PAD row 0 included); steps i <= 1 may pick only ids of src not in ys,
+ *             steps i >= 2 any id not in ys; argmax (ties -> lowest id); stop after EOS = n_rows - 1 or max_len - 1 generated tokens.
+ * Supported shape (anything else: DR4SR_E_SHAPE): D = 64, H = 2, F = 256, n_layer = 2 (encoder and decoder), K <= 5, 50 position rows,
+ * 2 <= max_len <= 25, source rows of at most 50 ids.
+ * Flat parameter layout (fp32; state-dict names of the reference's Generator):
+ *   [0] E[n_rows,D] item_embedding.weight (= item_embedding_decoder.weight)   [1] P[50,D] position_embedding.weight
+ *   per encoder layer i, [2+12*i+j]: transformer.encoder.layers.{i}.
+ *        self_attn.in_proj_weight[3D,D] self_attn.in_proj_bias[3D] self_attn.out_proj.weight[D,D] self_attn.out_proj.bias[D]
+ *        linear1.weight[F,D] linear1.bias[F] linear2.weight[D,F] linear2.bias[D] norm1.weight norm1.bias norm2.weight norm2.bias
+ *   [26] transformer.encoder.norm.weight  [27] transformer.encoder.norm.bias
+ *   per decoder layer i, [28+18*i+j]: transformer.decoder.layers.{i}.
+ *        self_attn.{in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias}
+ *        multihead_attn.{in_proj_weight[3D,D], in_proj_bias[3D], out_proj.weight, out_proj.bias}
+ *        linear1.weight linear1.bias linear2.weight linear2.bias norm1.weight norm1.bias norm2.weight norm2.bias norm3.weight norm3.bias
+ *   [64] transformer.decoder.norm.weight  [65] transformer.decoder.norm.bias
+ *   [66] condition_linear.0.weight[K*D,D]  [67] condition_linear.0.bias[K*D]  [68] condition_linear.2.weight[K*D,K*D]
+ *   [69] condition_linear.2.bias[K*D]                                      (condition_encoder.* is not used at inference) */
+#define DR4SR_REGEN_TENSORS 70
+typedef struct dr4sr_regen_plan {
+    int32_t abi_version;            /* must be DR4SR_ABI_VERSION                                                               */
+    int32_t n_rows;                 /* table rows N + 2 (SOS = N, EOS = N + 1; N counts PAD)                                  */
+    int32_t K;                      /* conditions (condition_linear.2.weight is [64K, 64K])                                    */
+    int32_t max_len;                /* the reference's max_len (25): at most max_len - 1 generated tokens                     */
+    int32_t D, H, F, n_layer;       /* 64, 2, 256, 2                                                                          */
+    float   ln_eps;                 /* layer_norm_eps (1e-12)                                                                  */
+    const float* params;            /* [n_params] in the layout above                                                         */
+    int64_t n_params;
+} dr4sr_regen_plan;
+int dr4sr_regen_plan_sizeof(void);
+/* fills offsets[0..DR4SR_REGEN_TENSORS) (may be NULL) for the supported shape; returns n_params, or DR4SR_E_ARG for n_rows < 3 / K < 1 */
+int64_t dr4sr_regen_param_layout(int32_t n_rows, int32_t K, int64_t* offsets);
+/* bytes of scratch for a call over n_seq source rows and n_cond conditions (R = n_seq * n_cond decode rows: about 77 KB per row),
+ * or DR4SR_E_SHAPE / DR4SR_E_ARG */
+int64_t dr4sr_regen_workspace_bytes(const dr4sr_regen_plan* plan, int64_t n_seq, int32_t n_cond);
+/* src [n_seq, Lsrc] int64 ids (row s holds src_len[s] ids: [SOS] + items + [EOS]; the rest is ignored), src_len [n_seq] int64.
+ * Lsrc > 50 (the reference's position table) -> DR4SR_E_SHAPE.  Ids are clamped to [0, n_rows) and src_len to [1, Lsrc] on the device.
+ * dr4sr_regen_encode fills the workspace with the cross-attention K | V of conditions cond0 .. cond0 + n_cond - 1 (cond0 + n_cond <= K);
+ * dr4sr_regen_decode then enqueues all max_len - 1 steps for the R = n_cond * n_seq rows, condition-major (row c * n_seq + s decodes
+ * source s under condition cond0 + c), and writes tokens [R, max_len] int64 (tokens[r, 0] = SOS; entries at or past len[r] are 0) and
+ * len [R] int32 (the number of valid entries of tokens[r], SOS included).  Both calls take the same src / src_len / n_seq / n_cond /
+ * workspace; the results do not depend on n_seq (a row decodes bit-identically alone or in any batch). */
+int dr4sr_regen_encode(const dr4sr_regen_plan* plan, const int64_t* src, const int64_t* src_len, int64_t n_seq, int32_t Lsrc,
+                       int32_t cond0, int32_t n_cond, void* workspace, int64_t workspace_bytes, void* stream);
+int dr4sr_regen_decode(const dr4sr_regen_plan* plan, const int64_t* src, const int64_t* src_len, int64_t n_seq, int32_t Lsrc,
+                       int32_t cond0, int32_t n_cond, void* workspace, int64_t workspace_bytes, int64_t* tokens, int32_t* len,
+                       void* stream);
 
 /* Test / measurement hooks (dr4sr_dropout_mask, dr4sr_*_launch_kernel) are NOT part of this product surface: they are declared in
  * include/dr4sr_hip_hooks.h, and nothing under dr4sr_amd/ calls them. */
