@@ -27,6 +27,8 @@ struct LayerWs {
     float* du1;    // [T,D]   d(LayerNorm1 input) (residual branch of qkv_bwd)
     float* dout;   // [T,D]   d(out_proj output) = du1 * dropout1 mask
     float* dqkv;   // [T,3D]
+    unsigned short* row_keep;  // [T,16] dropout keep bits of the three row passes (sP | sF << 4 | sA << 8 per thread of the 16-lane row group), saved by
+                               // k_post_fwd<16, 64, 128, .., KB> for k_post_bwd<.., KB> (linear.hip row_keep_saved)
 };
 
 struct Workspace {
@@ -142,6 +144,7 @@ struct alignas(16) PostArgs {                   // (16: the argument block behin
     float* dn_dqkv_zero;                       // backward: the K | V rows of layer-1's dqkv, zeroed by the launch in front of their accumulation
     int wt_attn;                               // wave-tile forward kernels (linear_wave.hip), round 6: 1 = the layer's attention forward runs at the head of every tile
                                                // (wt_attn_ctx: from at.qkv / at.tok; ctx, statistics and keep bits are still stored for the backward) — no attention launch
+    unsigned short* row_keep;                  // this layer's LayerWs::row_keep
     const unsigned short* sp;                  // bf16x3 tile GEMMs (d = 128 at scale): this layer's split-weight block, layer + 1's right behind (common.h); NULL: fp32.
                                                // Latency forms at d = 128 (16-row tiles): this layer's fragment-major fp32 image instead (as float*; layer + 1's E floats behind)
 };

@@ -346,19 +346,43 @@ int launch_embqkv_fwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int train
 
 // ------------------------------------------------------------------------------------------------
 
+// Row state that the forward half of k_post_mid<16, 64, ...> hands to its backward half in registers.  ln_rowpass / the GELU pass and
+// ln_bwd_rowpass / the da pass use the SAME thread <-> element map (row = threadIdx.x >> 4, c = 4 * (threadIdx.x & 15) + 64 j), so what
+// the backward row passes would load right behind a barrier (u, (mean, rstd), a) or regenerate (the Philox keep decisions) is what this
+// thread held a few microseconds earlier.  The forward still stores u1 / u2 / st1 / st2 / a (other entry points read them); the carried
+// values equal the stored ones bit for bit.  Keep decisions travel as bits (bit k = element c + k is kept), not as float factors.
+// The same struct serves the layers whose two halves are two launches (k_post_fwd -> k_post_bwd, 16-row tiles at d = 64): the forward stores only
+// the keep decisions, 16 bits per thread (LayerWs::row_keep, row_keep_store below), the backward requests its thread's u2 / st2 / a / u1 /
+// st1 and that word at kernel entry and runs its row passes from registers.
+// Modes (template int CARRY):   forward 0 nothing | 1 everything stays in registers (k_post_mid) | 2 keep bits stored (k_post_fwd<.., KB>)
+//                               backward 0 loads + Philox inside the passes | 1 registers of the forward half | 2 loads at entry, Philox | 3 loads at entry, saved bits
+struct LnCarry { float4 v; float mean, rstd; uint32_t keep; };
+template <int F>
+struct RowCarry { LnCarry ln1, ln2; float4 a[F / 64]; uint32_t akeep; };       // akeep: 4 bits per float4 of the activation dropout
+__host__ __device__ constexpr bool carry_vals(int CARRY) { return CARRY != 0; }
+__host__ __device__ constexpr bool carry_bits(int CARRY) { return CARRY == 1 || CARRY == 3; }
+__device__ __forceinline__ uint32_t keep_bits4(const float4& m) {              // m: factors of drop4 (0 or 1 / (1 - p) > 0)
+    return (m.x != 0.f ? 1u : 0u) | (m.y != 0.f ? 2u : 0u) | (m.z != 0.f ? 4u : 0u) | (m.w != 0.f ? 8u : 0u);
+}
+__device__ __forceinline__ float4 keep_factors4(const RngKey& k, uint32_t bits) {
+    return make_float4((bits & 1u) ? k.scale : 0.f, (bits & 2u) ? k.scale : 0.f, (bits & 4u) ? k.scale : 0.f, (bits & 8u) ? k.scale : 0.f);
+}
+
 // dropout + residual + LayerNorm over the 64 rows of a C tile held in LDS, 16 lanes per row, all four row passes of
 // a thread issued together (loads first, then four independent reduction chains, then stores) so that the single wave
 // per SIMD overlaps global-load / shuffle / Philox latencies across rows instead of serialising them.
 //   v = res + drop(C)  -> U (global);  LN(v) -> OUT (global) [+ LDS copy];  (mean, rstd) -> ST
 //   yreg (optional): the LayerNorm output rows of THIS thread ([pass][D/64] float4, zero beyond T) — with OUT == NULL nothing of
 //   them goes to global memory (the fused last layer hands them to the scorer in registers)
-template <int BM, int D, bool RES_IN_LDS, bool COPY_LDS>
+//   CARRY (one pass, one float4 per thread): v, (mean, rstd) and the keep bits of this thread's row are left in *cy as well
+template <int BM, int D, bool RES_IN_LDS, bool COPY_LDS, bool CARRY = false>
 __device__ __forceinline__ void ln_rowpass(const float* __restrict__ Cs, int ldc, const float* res, int ldres,
                                            const float* __restrict__ lnw, const float* __restrict__ lnb, float eps,
                                            float* __restrict__ U, float* __restrict__ OUT, float* __restrict__ ST,
                                            float* Ls, int ldl, int t0, int T, bool dodrop, const RngKey& rk,
-                                           uint32_t site, float4 (*yreg)[D / 64] = nullptr) {
+                                           uint32_t site, float4 (*yreg)[D / 64] = nullptr, LnCarry* cy = nullptr) {
     constexpr int NV = D / 64, PASSES = BM / 16;
+    static_assert(!CARRY || (NV == 1 && PASSES == 1), "the carried row state is one float4 per thread");
     const int l16 = threadIdx.x & 15, rsub = threadIdx.x >> 4;
     float4 gam[NV], bet[NV], v[PASSES][NV];
     float mean[PASSES], rstd[PASSES];
@@ -375,13 +399,17 @@ __device__ __forceinline__ void ln_rowpass(const float* __restrict__ Cs, int ldc
             float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
             if (RES_IN_LDS) r = ld4(res + row * ldres + c);
             else if (ok) r = ld4(res + (size_t)t * ldres + c);
-            if (dodrop) { const float4 m = drop4(rk, site, (uint64_t)t * D + c); o.x *= m.x; o.y *= m.y; o.z *= m.z; o.w *= m.w; }
+            if (dodrop) {
+                const float4 m = drop4(rk, site, (uint64_t)t * D + c); o.x *= m.x; o.y *= m.y; o.z *= m.z; o.w *= m.w;
+                if constexpr (CARRY) cy->keep = keep_bits4(m);
+            }
             v[ps][j] = make_float4(r.x + o.x, r.y + o.y, r.z + o.z, r.w + o.w);
             if (ok) st4(U + (size_t)t * D + c, v[ps][j]);
         }
     }
 #pragma unroll
     for (int ps = 0; ps < PASSES; ++ps) ln_stats16<NV>(v[ps], mean[ps], rstd[ps], eps);
+    if constexpr (CARRY) { cy->v = v[0][0]; cy->mean = mean[0]; cy->rstd = rstd[0]; }
 #pragma unroll
     for (int ps = 0; ps < PASSES; ++ps) {
         const int row = ps * 16 + rsub, t = t0 + row;
@@ -400,9 +428,16 @@ __device__ __forceinline__ void ln_rowpass(const float* __restrict__ Cs, int ldc
     }
 }
 
-template <int BM, int D, int F, bool FFN_ONLY, bool KEEPQ = false>
+// the 16 keep bits of a thread's three row passes (F = 128): sP | sF << 4 | sA << 8, at row_keep[16 t + (threadIdx.x & 15)]
+template <int F>
+__device__ __forceinline__ void row_keep_store(const PostArgs& A, const RowCarry<F>& cy, const int t0, const int T) {
+    static_assert(F == 128, "16 bits per thread");
+    const int t = t0 + (threadIdx.x >> 4);
+    if (t < T) A.row_keep[16 * (size_t)t + (threadIdx.x & 15)] = (unsigned short)(cy.ln1.keep | (cy.ln2.keep << 4) | (cy.akeep << 8));
+}
+template <int BM, int D, int F, bool FFN_ONLY, bool KEEPQ = false, int CARRY = 0>
 __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, const int T, float4 (*zreg)[D / 64] = nullptr,
-                                              tattn::Keep* keep_out = nullptr) {
+                                              tattn::Keep* keep_out = nullptr, RowCarry<F>* cy = nullptr) {
     constexpr int LD = D + 4, LF = F + 4, NVF = F / 64, PASSES = BM / 16;
     float* R0 = smem;                 // [64][LD]  ctx tile, later linear2 output
     float* R1 = R0 + BM * LD;         // [64][LD]  y tile
@@ -487,7 +522,8 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
         }
         lds_barrier(); STAMP(2);
         // ---- dropout1 + residual + LayerNorm1
-        ln_rowpass<BM, D, false, true>(R2, LD, A.x, D, A.ln1_w, A.ln1_b, A.eps, A.u1, A.y, A.st1, R1, LD, t0, T, dodrop, rk, sP);
+        ln_rowpass<BM, D, false, true, CARRY != 0>(R2, LD, A.x, D, A.ln1_w, A.ln1_b, A.eps, A.u1, A.y, A.st1, R1, LD, t0, T, dodrop, rk, sP, nullptr,
+                                              CARRY ? &cy->ln1 : nullptr);
     }
     lds_barrier(); STAMP(3);
     // ---- linear1 + GELU + dropout
@@ -514,7 +550,11 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
                 const int c = 4 * l16 + 64 * j;
                 const float4 a4 = av[ps][j];
                 float4 h = make_float4(gelu_erf(a4.x), gelu_erf(a4.y), gelu_erf(a4.z), gelu_erf(a4.w));
-                if (actdrop) { const float4 m = drop4(rk, sA, (uint64_t)t * F + c); h.x *= m.x; h.y *= m.y; h.z *= m.z; h.w *= m.w; }
+                if constexpr (CARRY != 0) { cy->a[j] = a4; if (j == 0) cy->akeep = 0; }
+                if (actdrop) {
+                    const float4 m = drop4(rk, sA, (uint64_t)t * F + c); h.x *= m.x; h.y *= m.y; h.z *= m.z; h.w *= m.w;
+                    if constexpr (CARRY != 0) cy->akeep |= keep_bits4(m) << (4 * j);
+                }
                 if (ok) { st4(A.a + (size_t)t * F + c, a4); st4(A.h + (size_t)t * F + c, h); }
                 st4(R2 + row * LF + c, h);
             }
@@ -531,7 +571,9 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
     }
     lds_barrier(); STAMP(6);
     if (!FFN_ONLY && A.nx_qkv) {               // layer-boundary fusion: keep z in LDS and emit the next layer's in_proj
-        ln_rowpass<BM, D, true, true>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, R1, LD, t0, T, dodrop, rk, sF);
+        ln_rowpass<BM, D, true, true, CARRY != 0>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, R1, LD, t0, T, dodrop, rk, sF, nullptr,
+                                                  CARRY ? &cy->ln2 : nullptr);
+        if constexpr (CARRY == 2) row_keep_store<F>(A, *cy, t0, T);
         lds_barrier();
         TileAcc<BM, 3 * D> acc;
         tile_zero(acc);
@@ -540,16 +582,24 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
         tile_to_global<BM, 3 * D>(acc, A.nx_qkv, 3 * D, A.nx_in_b, t0, T);
         if (A.nx_dqkv_zero) zero_kv_rows<BM, D>(A.nx_dqkv_zero, t0, T);
     } else {
-        ln_rowpass<BM, D, true, false>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, nullptr, 0, t0, T, dodrop, rk, sF, zreg);
+        ln_rowpass<BM, D, true, false, CARRY != 0>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, nullptr, 0, t0, T, dodrop, rk, sF, zreg,
+                                                   CARRY ? &cy->ln2 : nullptr);
+        if constexpr (CARRY == 2) row_keep_store<F>(A, *cy, t0, T);
     }
     STAMP(15);
 }
 
-template <int BM, int D, int F, bool FFN_ONLY>
+// KB (host: row_keep_saved — training with dropout, 16-row tiles, d = 64, F = 128, fused step): the keep decisions of the three row passes are
+// stored for k_post_bwd<.., KB>; the two launches of a plan are paired by that ONE predicate
+template <int BM, int D, int F, bool FFN_ONLY, bool KB = false>
 __global__ __launch_bounds__(256) void k_post_fwd(const PostArgs A) {
     const int T = A.state[DR4SR_STATE_T], t0 = xcd_tile(T, BM, A.xcd) * BM;
     if (t0 >= T) return;
-    post_fwd_body<BM, D, F, FFN_ONLY>(A, t0, T);
+    if constexpr (KB) {
+        RowCarry<F> cy;
+        cy.ln1.keep = cy.ln2.keep = cy.akeep = 0;
+        post_fwd_body<BM, D, F, FFN_ONLY, false, 2>(A, t0, T, nullptr, nullptr, &cy);
+    } else post_fwd_body<BM, D, F, FFN_ONLY>(A, t0, T);
 }
 
 // fold the 16 row-groups of the workgroup (4 per wave x 4 waves) into ONE partial row per token tile:
@@ -576,15 +626,19 @@ __device__ __forceinline__ void flush_affine(const float4 (&dgam)[NV], const flo
 // LayerNorm backward over the 64 rows of a tile with the four row passes of a thread issued together (see ln_rowpass).
 //   g = Gg[t] (SRC 0) | La[row] + Lb[row] (SRC 1) | La[row] + Gg[t] (SRC 2);   du = LN'(g; u, mean, rstd, gamma)
 //   du -> DUg (global, optional) and DUl (LDS, optional);   du * dropout(site) -> DMg (global) and DMl (LDS)
-template <int BM, int D, int SRC>
+//   CARRY != 0: u and (mean, rstd) come from *cy (left by this thread's ln_rowpass, or loaded at kernel entry) — no Ug / ST loads here;
+//   CARRY 1 | 3: the keep decisions too — no Philox call
+template <int BM, int D, int SRC, int CARRY = 0>
 __device__ __forceinline__ void ln_bwd_rowpass(const float* __restrict__ Gg, const float* La,
                                                const float* Lb, int ldl, const float* __restrict__ Ug,
                                                const float* __restrict__ ST, const float* __restrict__ lnw,
                                                float* __restrict__ DUg, float* DUl, float* __restrict__ DMg,
                                                float* DMl, float4 (&dgam)[D / 64], float4 (&dbet)[D / 64],
                                                int t0, int T, bool dodrop, const RngKey& rk, uint32_t site,
-                                               const float4 (*greg)[D / 64] = nullptr) {
+                                               const float4 (*greg)[D / 64] = nullptr, const LnCarry* cy = nullptr) {
     constexpr int NV = D / 64, PASSES = BM / 16;
+    static_assert(!CARRY || (NV == 1 && PASSES == 1), "the carried row state is one float4 per thread");
+    constexpr bool VALS = carry_vals(CARRY), BITS = carry_bits(CARRY);
     const int l16 = threadIdx.x & 15, rsub = threadIdx.x >> 4;
     float4 gam[NV], g[PASSES][NV], u[PASSES][NV];
     float mean[PASSES], rstd[PASSES];
@@ -598,13 +652,14 @@ __device__ __forceinline__ void ln_bwd_rowpass(const float* __restrict__ Gg, con
     for (int ps = 0; ps < PASSES; ++ps) {
         const int row = ps * 16 + rsub, t = t0 + row;
         const bool ok = t < T;
-        mean[ps] = ok ? ST[2 * (size_t)t] : 0.f;
-        rstd[ps] = ok ? ST[2 * (size_t)t + 1] : 0.f;
+        if constexpr (VALS) { mean[ps] = ok ? cy->mean : 0.f; rstd[ps] = ok ? cy->rstd : 0.f; }
+        else { mean[ps] = ok ? ST[2 * (size_t)t] : 0.f; rstd[ps] = ok ? ST[2 * (size_t)t + 1] : 0.f; }
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const int c = 4 * l16 + 64 * j;
             const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            u[ps][j] = ok ? ld4(Ug + (size_t)t * D + c) : z4;
+            if constexpr (VALS) u[ps][j] = ok ? cy->v : z4;
+            else u[ps][j] = ok ? ld4(Ug + (size_t)t * D + c) : z4;
             if (SRC == 0) g[ps][j] = ok ? ld4(Gg + (size_t)t * D + c) : z4;
             else if (SRC == 3) g[ps][j] = ok ? greg[ps][j] : z4;     // this thread's rows, straight from the scorer (registers)
             else {
@@ -629,7 +684,11 @@ __device__ __forceinline__ void ln_bwd_rowpass(const float* __restrict__ Gg, con
             if (DUg && ok) st4(DUg + (size_t)t * D + c, du);
             if (DUl) st4(DUl + row * ldl + c, du);
             float4 dm = du;
-            if (dodrop) { const float4 m = drop4(rk, site, (uint64_t)t * D + c); dm.x *= m.x; dm.y *= m.y; dm.z *= m.z; dm.w *= m.w; }
+            if (dodrop) {
+                float4 m;
+                if constexpr (BITS) m = keep_factors4(rk, cy->keep); else m = drop4(rk, site, (uint64_t)t * D + c);
+                dm.x *= m.x; dm.y *= m.y; dm.z *= m.z; dm.w *= m.w;
+            }
             if (ok) st4(DMg + (size_t)t * D + c, dm);
             st4(DMl + row * ldl + c, dm);
         }
@@ -638,9 +697,12 @@ __device__ __forceinline__ void ln_bwd_rowpass(const float* __restrict__ Gg, con
 
 // DET: the deterministic latency form (kernels.h Workspace::det_lat) — a separate instantiation: as a run-time branch it cost the default step
 // 0.8 % (d = 64) / 2 % (d = 128) at B = 256
-template <int BM, int D, int F, bool FFN_ONLY, bool DET = false>
+// CARRY (RowCarry above): 1 (k_post_mid<16, 64, ...>) the three row passes take their saved activations and keep decisions from *cy_in;
+// 2 | 3 (k_post_bwd<16, 64, ...>) this thread's u2 / st2 / a / u1 / st1 [and keep word: 3] are requested at kernel entry
+template <int BM, int D, int F, bool FFN_ONLY, bool DET = false, int CARRY = 0>
 __device__ __forceinline__ void post_bwd_body(const PostArgs& A, const int t0, const int T, const int tile,
-                                              const float4 (*dzreg)[D / 64] = nullptr, const tattn::Keep* att_staged = nullptr) {
+                                              const float4 (*dzreg)[D / 64] = nullptr, const tattn::Keep* att_staged = nullptr,
+                                              const RowCarry<F>* cy_in = nullptr) {
     constexpr int LD = D + 4, LF = F + 4, NV = D / 64, NVF = F / 64, PASSES = BM / 16;
     float* R1 = smem;                          // R1 first: R0 and R2 are contiguous and together hold a [64][3D+4] dqkv tile
     float* R0 = R1 + BM * LD;
@@ -674,6 +736,8 @@ __device__ __forceinline__ void post_bwd_body(const PostArgs& A, const int t0, c
     constexpr int UPQ = AT ? (16 * 3 * D / 4) / 256 : 1;
     float4 updq[UPQ];
     bool up_pre = false;
+    RowCarry<F> cy_ld;
+    const RowCarry<F>* cy = CARRY >= 2 ? &cy_ld : cy_in;
     if constexpr (AT) {
         at_on = A.at.on != 0;
         at_stage = at_on && !att_staged;
@@ -692,6 +756,28 @@ __device__ __forceinline__ void post_bwd_body(const PostArgs& A, const int t0, c
                 if (t0 + row < T) updq[q] = ld4(A.up_dqkv + (size_t)(t0 + row) * 3 * D + c);
             }
             if constexpr (PF64) wfrag_load(fr_up, A.up_in_w, D);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (CARRY >= 2) {
+            // the row passes' saved activations: their addresses need t0 only, so they are requested here — behind the first phase's own
+            // tile, in front of the attention's window (same order argument) — instead of right behind the barrier in front of each pass
+            static_assert(D == 64 && BM == 16, "one row, one float4 per thread");
+            const int t = t0 + rsub, c = 4 * l16;
+            const bool ok = t < T;
+            const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float2 z2 = make_float2(0.f, 0.f);
+            cy_ld.ln2.v = ok ? ld4(A.u2 + (size_t)t * D + c) : z4;
+            const float2 s2 = ok ? *reinterpret_cast<const float2*>(A.st2 + 2 * (size_t)t) : z2;
+#pragma unroll
+            for (int j = 0; j < NVF; ++j) cy_ld.a[j] = ok ? ld4(A.a + (size_t)t * F + c + 64 * j) : z4;
+            cy_ld.ln1.v = ok ? ld4(A.u1 + (size_t)t * D + c) : z4;
+            const float2 s1 = ok ? *reinterpret_cast<const float2*>(A.st1 + 2 * (size_t)t) : z2;
+            cy_ld.ln2.mean = s2.x; cy_ld.ln2.rstd = s2.y; cy_ld.ln1.mean = s1.x; cy_ld.ln1.rstd = s1.y;
+            cy_ld.ln1.keep = cy_ld.ln2.keep = cy_ld.akeep = 0;
+            if constexpr (CARRY == 3) {
+                const uint32_t w = ok ? (uint32_t)A.row_keep[16 * (size_t)t + l16] : 0u;
+                cy_ld.ln1.keep = w & 15u; cy_ld.ln2.keep = (w >> 4) & 15u; cy_ld.akeep = w >> 8;
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
         if (at_stage) {
@@ -730,13 +816,16 @@ __device__ __forceinline__ void post_bwd_body(const PostArgs& A, const int t0, c
         else { tile_gemm<BM == 32 && (D == 128 || FFN_ONLY), BM, 3 * D, D>(Aq, LQ, A.up_in_w, D, true, A.sp ? A.sp + 4 * WSplitGeo<D, F>::E : nullptr, WSplitGeo<D, F>::E, 0, acc); if constexpr (PF128) wfrag_load(fr_w2, A.w2, F); }
         tile_to_lds<BM, D>(acc, R1, LD, nullptr);
         lds_barrier();
-        ln_bwd_rowpass<BM, D, 2>(A.up_du1, R1, nullptr, LD, A.u2, A.st2, A.ln2_w, nullptr, R1, A.df, R0, dgam, dbet, t0, T, dodrop, rk, sF);
+        ln_bwd_rowpass<BM, D, 2, CARRY>(A.up_du1, R1, nullptr, LD, A.u2, A.st2, A.ln2_w, nullptr, R1, A.df, R0, dgam, dbet, t0, T, dodrop, rk, sF, nullptr,
+                                        CARRY ? &cy->ln2 : nullptr);
     } else if (dzreg) {
         att_commit();
-        ln_bwd_rowpass<BM, D, 3>(nullptr, nullptr, nullptr, LD, A.u2, A.st2, A.ln2_w, nullptr, R1, A.df, R0, dgam, dbet, t0, T, dodrop, rk, sF, dzreg);
+        ln_bwd_rowpass<BM, D, 3, CARRY>(nullptr, nullptr, nullptr, LD, A.u2, A.st2, A.ln2_w, nullptr, R1, A.df, R0, dgam, dbet, t0, T, dodrop, rk, sF, dzreg,
+                                        CARRY ? &cy->ln2 : nullptr);
     } else {
         att_commit();
-        ln_bwd_rowpass<BM, D, 0>(A.dz, nullptr, nullptr, LD, A.u2, A.st2, A.ln2_w, nullptr, R1, A.df, R0, dgam, dbet, t0, T, dodrop, rk, sF);
+        ln_bwd_rowpass<BM, D, 0, CARRY>(A.dz, nullptr, nullptr, LD, A.u2, A.st2, A.ln2_w, nullptr, R1, A.df, R0, dgam, dbet, t0, T, dodrop, rk, sF, nullptr,
+                                        CARRY ? &cy->ln2 : nullptr);
     }
     flush_affine<NV>(dgam, dbet, R2, A.ln_part + (size_t)tile * 4 * D);
     // ---- dh = df W2   (x W^T form with W2^T [F][D])
@@ -759,8 +848,13 @@ __device__ __forceinline__ void post_bwd_body(const PostArgs& A, const int t0, c
             float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
             if (t < T) {
                 d = ld4(R2 + row * LF + c);
-                const float4 av = ld4(A.a + (size_t)t * F + c);
-                if (actdrop) { const float4 m = drop4(rk, sA, (uint64_t)t * F + c); d.x *= m.x; d.y *= m.y; d.z *= m.z; d.w *= m.w; }
+                float4 av;
+                if constexpr (carry_vals(CARRY)) av = cy->a[j]; else av = ld4(A.a + (size_t)t * F + c);
+                if (actdrop) {
+                    float4 m;
+                    if constexpr (carry_bits(CARRY)) m = keep_factors4(rk, cy->akeep >> (4 * j)); else m = drop4(rk, sA, (uint64_t)t * F + c);
+                    d.x *= m.x; d.y *= m.y; d.z *= m.z; d.w *= m.w;
+                }
                 d.x *= gelu_erf_grad(av.x); d.y *= gelu_erf_grad(av.y); d.z *= gelu_erf_grad(av.z); d.w *= gelu_erf_grad(av.w);
                 st4(A.da + (size_t)t * F + c, d);
             }
@@ -789,7 +883,8 @@ __device__ __forceinline__ void post_bwd_body(const PostArgs& A, const int t0, c
         }
         return;
     }
-    ln_bwd_rowpass<BM, D, 1>(nullptr, R0, R1, LD, A.u1, A.st1, A.ln1_w, A.du1, nullptr, A.dout, R1, dgam, dbet, t0, T, dodrop, rk, sP);
+    ln_bwd_rowpass<BM, D, 1, CARRY>(nullptr, R0, R1, LD, A.u1, A.st1, A.ln1_w, A.du1, nullptr, A.dout, R1, dgam, dbet, t0, T, dodrop, rk, sP, nullptr,
+                                    CARRY ? &cy->ln1 : nullptr);
     flush_affine<NV>(dgam, dbet, R2, A.ln_part + (size_t)tile * 4 * D + 2 * D);
     // ---- dctx = do W_out
     {
@@ -828,11 +923,13 @@ __device__ __forceinline__ void post_bwd_body(const PostArgs& A, const int t0, c
     STAMP(26);
 }
 
-template <int BM, int D, int F, bool FFN_ONLY, bool DET = false>
+// KB: the keep decisions k_post_fwd<.., KB> stored (every other form regenerates them — the cross-check)
+template <int BM, int D, int F, bool FFN_ONLY, bool DET = false, bool KB = false>
 __global__ __launch_bounds__(256) void k_post_bwd(const PostArgs A) {
     const int T = A.state[DR4SR_STATE_T], bx = xcd_tile(T, BM, A.xcd), t0 = bx * BM;
     if (t0 >= T) return;
-    post_bwd_body<BM, D, F, FFN_ONLY, DET>(A, t0, T, bx);
+    constexpr int CARRY = (BM == 16 && D == 64 && !FFN_ONLY) ? (KB ? 3 : 2) : 0;
+    post_bwd_body<BM, D, F, FFN_ONLY, DET, CARRY>(A, t0, T, bx);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1290,12 +1387,14 @@ __device__ __forceinline__ void post_mid_body(const PostArgs& A, const ScoreTile
         PostArgs Af = A;
         if (!S.rec) Af.z = nullptr;                          // the query rows leave the kernel only when the owner job will gather them
         tattn::Keep keep{0xffffffffu, 0xffffffffu};
-        post_fwd_body<BM, D, F, false, true>(Af, t0, T, zreg, &keep);
+        constexpr int CARRY = BM == 16 ? 1 : 0;              // latency regime: the row passes' state crosses the two halves in registers
+        RowCarry<F> cy;
+        post_fwd_body<BM, D, F, false, true, CARRY>(Af, t0, T, zreg, &keep, &cy);
         if constexpr (BM != 16) score_prefetch<BM>(A, S, t0, T, P);             // occupancy regime: its registers would cost a workgroup per CU
         if constexpr (META) lds_barrier();                   // every wave is past the forward half's last LDS reads: the tiles are free
         score_tile_regs<BM, META>(A, S, t0, T, bx, P, zreg, dzreg, smem + post_lds_floats(D, F, BM), smem);
         if constexpr (BM != 16) { if (S.ent) tile_sort<BM>(S, bx, t0, T, smem + post_lds_floats(D, F, BM) + 8); }
-        post_bwd_body<BM, D, F, false, DET>(A, t0, T, bx, dzreg, &keep);
+        post_bwd_body<BM, D, F, false, DET, CARRY>(A, t0, T, bx, dzreg, &keep, &cy);
     } else {
         tattn::Keep keep{0xffffffffu, 0xffffffffu};
         post_fwd_body<BM, D, F, false, true>(A, t0, T, nullptr, &keep);
@@ -1356,6 +1455,7 @@ PostArgs make_post_args(const dr4sr_sasrec_plan* p, const Workspace& ws, int lay
     if (wfrag_img_on(p, ws)) A.sp = reinterpret_cast<const unsigned short*>(ws.wfrag + (size_t)layer * ws.wT_stride);
     A.at.kv_part = (A.at.on && ws.det_lat && ws.det_kv) ? ws.det_kv + (size_t)layer * ws.det_kv_layer : nullptr;
     A.up_kv_part = (A.at.kv_part && A.up_dqkv) ? ws.det_kv + (size_t)(layer + 1) * ws.det_kv_layer : nullptr;
+    A.row_keep = lw.row_keep;
     A.nx_dqkv_zero = (A.at.on && A.nx_qkv) ? ws.layer[layer + 1].dqkv : nullptr;
     A.dn_dqkv_zero = (A.at.on && layer > 0) ? ws.layer[layer - 1].dqkv : nullptr;
     return A;
@@ -1363,11 +1463,27 @@ PostArgs make_post_args(const dr4sr_sasrec_plan* p, const Workspace& ws, int lay
 
 static size_t post_lds(int D, int F, int bm = 64) { return sizeof(float) * post_lds_floats(D, F, bm); }
 
+// ONE predicate for both launches of a plan: k_post_bwd may read saved row-pass keep bits only where the k_post_fwd of this plan wrote them.
+// Fused training step with dropout, 16-row tiles, d = 64, F = 128; evaluation and p = 0 write and read nothing; the 19-launch DR4SR_NO_FUSE
+// step and every other form regenerate the decisions with Philox (tests/test_gpu_r2_paths.py runs them against the oracle).
+static bool row_keep_saved(const dr4sr_sasrec_plan* p, const Workspace& ws, const PostArgs& A) {
+    return A.training && p->p_drop > 0.f && p->D == 64 && p->F == 128 && tile_rows(ws) == 16 && !wave_tiles(p, ws) && !DR4SR_ENV("DR4SR_NO_FUSE")
+           && A.row_keep != nullptr;
+}
+
 template <int BM>
 static int post_launch_bm(const dr4sr_sasrec_plan* p, const Workspace& ws, const PostArgs& A, bool bwd, hipStream_t s) {
     dim3 grid((ws.Tmax + BM - 1) / BM), blk(256);
     if (A.xcd) grid.x = xcd_grid((int)grid.x, BM);
     const size_t lds = (BM == 16 && A.at.on) ? sizeof(float) * att_lds_off(p->D, p->F) + att_lds_bytes(p->D) : post_lds(p->D, p->F, BM);
+    if constexpr (BM == 16) {
+        if (row_keep_saved(p, ws, A)) {                 // (d = 64, F = 128)
+            if (bwd && A.at.kv_part) { big_lds((k_post_bwd<16, 64, 128, false, true, true>), lds); hipLaunchKernelGGL((k_post_bwd<16, 64, 128, false, true, true>), grid, blk, lds, s, A); }
+            else if (bwd) { big_lds((k_post_bwd<16, 64, 128, false, false, true>), lds); hipLaunchKernelGGL((k_post_bwd<16, 64, 128, false, false, true>), grid, blk, lds, s, A); }
+            else { big_lds((k_post_fwd<16, 64, 128, false, true>), lds); hipLaunchKernelGGL((k_post_fwd<16, 64, 128, false, true>), grid, blk, lds, s, A); }
+            return DR4SR_LAUNCH_CHECK();
+        }
+    }
 #define PL(D_, F_) do { if (bwd && BM == 16 && A.at.kv_part) { big_lds((k_post_bwd<BM == 16 ? 16 : 64, D_, F_, false, BM == 16>), lds); \
                                                               hipLaunchKernelGGL((k_post_bwd<BM == 16 ? 16 : 64, D_, F_, false, BM == 16>), grid, blk, lds, s, A); } \
                         else if (bwd) { big_lds(k_post_bwd<BM, D_, F_, false>, lds); hipLaunchKernelGGL((k_post_bwd<BM, D_, F_, false>), grid, blk, lds, s, A); } \

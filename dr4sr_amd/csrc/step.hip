@@ -241,6 +241,9 @@ int carve_workspace(const dr4sr_sasrec_plan* p, Workspace* ws) {
         w.a = take(Tmax * F); w.h = take(Tmax * F); w.u2 = take(Tmax * D); w.st2 = take(Tmax * 2);
         w.df = take(Tmax * D); w.da = take(Tmax * F); w.du1 = take(Tmax * D); w.dout = take(Tmax * D); w.dqkv = take(Tmax * 3 * D);
     }
+    // row-pass keep bits of the latency-regime tile kernels (LayerWs::row_keep, 32 B per token slot and layer).  For EVERY workspace — the plans
+    // that share one differ in regime — and LAST: nothing carved above moves
+    for (int l = 0; l < p->n_layer; ++l) ws->layer[l].row_keep = reinterpret_cast<unsigned short*>(take(Tmax * 8));
     ws->bytes = o;
     return 0;
 }
