@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DR4SR_LIB_PATH") or os.path.join(_HERE, "csrc", "libdr4sr_hip.so")     # override: A/B runs of two builds on one box
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 COMM_ID_BYTES = 128           # DR4SR_COMM_ID_BYTES (the RCCL unique id, a host buffer)
 GRAD_TAIL = 4
 STATE_WORDS = 16
@@ -291,6 +291,10 @@ SYMBOLS = {
     "dr4sr_regen_encode": (C.c_int, [_RPLANP, _i64p, _i64p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "dr4sr_regen_decode": (C.c_int, [_RPLANP, _i64p, _i64p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _i64p,
                                      C.c_void_p, C.c_void_p]),
+    # ABI 10: the regenerator's pre-training pairs (csrc/pairs.hip)
+    "dr4sr_pairs_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
+    "dr4sr_pairs_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, _i64p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64,
+                                    C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dr4sr_crash_line_set": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32]),           # measurement hook (include/dr4sr_hip_hooks.h)
 }
 

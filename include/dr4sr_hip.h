@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define DR4SR_ABI_VERSION 9
+#define DR4SR_ABI_VERSION 10
 
 #define DR4SR_E_ARG      (-1)   /* null pointer / bad size                                   */
 #define DR4SR_E_SHAPE    (-2)   /* unsupported D / H / F / L combination     */
@@ -632,6 +632,31 @@ int dr4sr_regen_encode(const dr4sr_regen_plan* plan, const int64_t* src, const i
 int dr4sr_regen_decode(const dr4sr_regen_plan* plan, const int64_t* src, const int64_t* src_len, int64_t n_seq, int32_t Lsrc,
                        int32_t cond0, int32_t n_cond, void* workspace, int64_t workspace_bytes, int64_t* tokens, int32_t* len,
                        void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABI 10 — the regenerator's pre-training pairs (stage 1 of DR4SR, the second half of the reference's 1.Build_pretraining_dataset.py,
+ * lines 70-93: `shuffle(patterns_value)` per sequence, then is_sublist over the list until ten patterns matched), csrc/pairs.hip.
+ *   match(i, j) : pattern j is a subsequence of sequence i — not necessarily contiguous, repeated ids respected: the greedy left-most
+ *                 scan of is_sublist (:70-77).  A pattern longer than the sequence does not match.
+ *   n_match[i]  : the number m_i of matching patterns (all of them, not capped at 10).
+ *   chosen[i,:] : the min(10, m_i) matching patterns with the smallest (key, j), ascending, -1 padded, where
+ *                 key(i, j) = word x of philox4x32_10(counter = (seq_index0 + i, pat_index0 + j, 0x50414952, 0), key = (low, high 32 bits
+ *                 of seed)) — a uniformly random subset in uniformly random order (what "shuffle, take the first ten hits" draws, :79-93),
+ *                 a pure function of (seed, seq_index0 + i, pat_index0 + j): the same for any n_chunks, for any split of the sequences
+ *                 over calls (pass the first row's index in the file as seq_index0), and whatever else is in the batch.  The values
+ *                 written are pat_index0 + j.
+ * seqs [n_seq, Lmax] int32 ids with seq_len [n_seq] int32 valid ids per row (clamped to [0, Lmax] on the device; the rest of a row is
+ * ignored); patterns in ragged form: pat_ids [n_ids] int32 and pat_off [n_pat + 1] int64, pattern j = pat_ids[pat_off[j] : pat_off[j+1]].
+ * n_chunks: how many workgroups share the pattern list per tile of 32 sequences (1..64; 0 = chosen from the sizes).
+ * Checked on the host before anything is launched: null pointers, negative or >= 2^31 sizes and indices, n_chunks outside 0..64
+ * (DR4SR_E_ARG); Lmax > 64 (DR4SR_E_SHAPE); a null or too small workspace (DR4SR_E_WS).  NOT checked on the host: the contents of
+ * pat_off.  On the device a pattern whose offsets are not 0 <= pat_off[j] < pat_off[j+1] <= n_ids (non-monotonic offsets, an empty
+ * pattern) or that has more than 64 ids matches nothing, so nothing is read out of bounds; ids are compared as given, whatever their
+ * range.  Everything is enqueued on `stream`; there is no host synchronisation. */
+int64_t dr4sr_pairs_workspace_bytes(int64_t n_seq, int64_t n_pat, int32_t n_chunks);
+int dr4sr_pairs_match(const int32_t* seqs, const int32_t* seq_len, int64_t n_seq, int32_t Lmax, const int32_t* pat_ids,
+                      const int64_t* pat_off, int64_t n_pat, int64_t n_ids, uint64_t seed, int64_t seq_index0, int64_t pat_index0,
+                      int32_t n_chunks, void* workspace, int64_t workspace_bytes, int32_t* n_match, int32_t* chosen, void* stream);
 
 /* Test / measurement hooks (dr4sr_dropout_mask, dr4sr_*_launch_kernel) are NOT part of this product surface: they are declared in
  * include/dr4sr_hip_hooks.h, and nothing under dr4sr_amd/ calls them. */
