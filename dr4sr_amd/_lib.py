@@ -164,6 +164,7 @@ class RegenPlan(C.Structure):
 
 
 REGEN_TENSORS = 70            # DR4SR_REGEN_TENSORS
+REGEN_SCORE_TENSORS = 98      # DR4SR_REGEN_SCORE_TENSORS
 
 _PLANP = C.POINTER(SasrecPlan)
 _FPLANP = C.POINTER(FmlpPlan)
@@ -295,6 +296,12 @@ SYMBOLS = {
     "dr4sr_pairs_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
     "dr4sr_pairs_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, _i64p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64,
                                     C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # additive to ABI 10: teacher-forced scoring of the regenerator (csrc/regen_score.hip)
+    "dr4sr_regen_score_param_layout": (C.c_int64, [C.c_int32, C.c_int32, C.c_void_p]),
+    "dr4sr_regen_score_workspace_bytes": (C.c_int64, [_RPLANP, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "dr4sr_regen_score_condition": (C.c_int, [_RPLANP, _i64p, _i64p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, _f32p, C.c_void_p]),
+    "dr4sr_regen_score": (C.c_int, [_RPLANP, _i64p, _i64p, _i64p, _i64p, C.c_int64, C.c_int32, C.c_int32, _f32p, C.c_int32, C.c_int32,
+                                    C.c_void_p, C.c_int64, _f32p, C.c_void_p]),
     "dr4sr_crash_line_set": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32]),           # measurement hook (include/dr4sr_hip_hooks.h)
 }
 

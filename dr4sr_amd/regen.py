@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
+import json
 import math
 import os
 
@@ -28,6 +29,7 @@ D, H, FF, N_LAYER, N_POS, MAX_LEN, LN_EPS = 64, 2, 256, 2, 50, 25, 1e-12
 NUM_ITEM = {"toy": 11925, "sport": 18358, "beauty": 12102, "yelp": 20034}     # 3.Hybrid_inference.py:237-242
 ROWS_PER_CALL = 16384          # decode rows per HIP call: ~1.3 GB of workspace (csrc/regen.hip, about 77 KB per row)
 ROWS_PER_TORCH = 2048          # decode rows per torch batch ([rows, n_rows] logits)
+PAIRS_PER_CALL = 4096          # score(): pairs per HIP call (csrc/regen_score.hip keeps K x 2 x Ls x 128 floats per pair: 256 KB at Ls = 50)
 MAX_SEQ_LEN = 50
 
 _ENC = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias",
@@ -49,6 +51,19 @@ def param_names():
     return names
 
 
+def score_param_names():
+    """the 98 tensors of dr4sr_regen_score_param_layout: param_names() followed by condition_encoder.*"""
+    names = param_names()
+    names += [f"condition_encoder.encoder.layers.{i}.{n}" for i in range(N_LAYER) for n in _ENC]
+    names += [f"condition_encoder.condition_layer.{i}.{n}" for i in (0, 2) for n in ("weight", "bias")]
+    return names
+
+
+def score_param_shapes(n_rows: int, K: int):
+    enc = [(3 * D, D), (3 * D,), (D, D), (D,), (FF, D), (FF,), (D, FF), (D,), (D,), (D,), (D,), (D,)]
+    return param_shapes(n_rows, K) + enc * N_LAYER + [(D, D), (D,), (K, D), (K,)]
+
+
 def param_shapes(n_rows: int, K: int):
     enc = [(3 * D, D), (3 * D,), (D, D), (D,), (FF, D), (FF,), (D, FF), (D,), (D,), (D,), (D,), (D,)]
     dec = [(3 * D, D), (3 * D,), (D, D), (D,), (3 * D, D), (3 * D,), (D, D), (D,), (FF, D), (FF,), (D, FF), (D,)] + [(D,)] * 6
@@ -66,12 +81,15 @@ class RegenModel:
         self.sos, self.eos = self.n_item, self.n_item + 1
         self.p = {k: v.to(self.device, torch.float32).contiguous() for k, v in params.items()}
         self._flat = None
+        self._score_flat = None
+        self._cast = {}
+        self.has_condition_encoder = "condition_encoder.condition_layer.2.weight" in self.p
         self.record_gaps = None        # a list: the torch restatement appends (gap, top) [rows, 24] per batch it decodes
 
     @classmethod
     def from_state_dict(cls, sd: dict, device="cuda", dataset: str | None = None):
-        """`sd`: the reference's regenerator.pth as saved (2.Pretrain_regenerator.py:318).  condition_encoder.* is ignored (it is
-        only used in training); item_embedding_decoder.weight must be the same table as item_embedding.weight (the reference ties
+        """`sd`: the reference's regenerator.pth as saved (2.Pretrain_regenerator.py:318).  condition_encoder.* is kept when it is
+        complete (score() uses it; decoding never does) and dropped otherwise; item_embedding_decoder.weight must be the same table as item_embedding.weight (the reference ties
         them).  N and K come from the tensors; with a known `dataset` name N is checked against the reference's num_item_dict."""
         if "item_embedding.weight" not in sd or "condition_linear.2.weight" not in sd:
             raise ValueError("not a regenerator state dict: item_embedding.weight / condition_linear.2.weight missing")
@@ -93,6 +111,9 @@ class RegenModel:
             if tuple(sd[name].shape) != shape:
                 raise ValueError(f"{name}: shape {tuple(sd[name].shape)}, expected {shape}")
             params[name] = sd[name].detach()
+        extra = list(zip(score_param_names(), score_param_shapes(n_rows, K)))[len(params):]
+        if all(name in sd and tuple(sd[name].shape) == shape for name, shape in extra):     # a complete condition_encoder: kept for score()
+            params.update({name: sd[name].detach() for name, _ in extra})
         return cls(params, n_rows, K, device)
 
     # ------------------------------------------------------------------------------------------------ HIP
@@ -110,6 +131,29 @@ class RegenModel:
                 buf[off[i]:off[i] + t.numel()] = t
             self._flat = buf
         return self._flat
+
+    def score_flat(self):
+        """the flat fp32 parameter buffer of dr4sr_regen_score_param_layout (condition_encoder.* zero when the model has none)"""
+        if self._score_flat is None:
+            lib = _lib.load()
+            off = (C.c_int64 * _lib.REGEN_SCORE_TENSORS)()
+            n = lib.dr4sr_regen_score_param_layout(self.n_rows, self.K, off)
+            if n < 0:
+                _lib.check(int(n), "dr4sr_regen_score_param_layout")
+            buf = torch.zeros(int(n), dtype=torch.float32, device=self.device)
+            for i, name in enumerate(score_param_names()):
+                if name in self.p:
+                    t = self.p[name].reshape(-1)
+                    buf[off[i]:off[i] + t.numel()] = t
+            self._score_flat = buf
+        return self._score_flat
+
+    def score_plan(self):
+        p = self.plan()
+        flat = self.score_flat()
+        p.params = flat.data_ptr()
+        p.n_params = flat.numel()
+        return p
 
     def plan(self):
         p = _lib.RegenPlan()
@@ -308,8 +352,220 @@ class RegenModel:
         """the reference's translate(model, src) under set_condition(condition), for every source: one int64 tensor each"""
         return [torch.tensor(t, dtype=torch.int64) for t in self.decode(src_list, condition, 1, backend)]
 
+    # ------------------------------------------------------------------------------------------------ teacher-forced scoring
+    def _pack_pairs(self, pairs, width):
+        """the padded matrices of 2.Pretrain_regenerator.py:49-64 and :275-282: src [n, Ls], tgt_in / tgt_out [n, T], lengths with
+        SOS and EOS counted; Ls and T are the file-wide widths (`width` overrides the ones derived from `pairs`)"""
+        srcs = [[self.sos] + [int(v) for v in s] + [self.eos] for s, _ in pairs]
+        tgts = [[self.sos] + [int(v) for v in t] + [self.eos] for _, t in pairs]
+        Ls = max((len(s) for s in srcs), default=2)
+        T = max(20, max((len(t) for t in tgts), default=2)) - 1
+        if width is not None:
+            wl, wt = int(width[0]), int(width[1])
+            need_t = max((len(t) for t in tgts), default=2) - 1
+            if wl < Ls or wt < need_t:
+                raise ValueError(f"width {tuple(width)} is narrower than the pairs need ({Ls}, {need_t})")
+            Ls, T = wl, wt
+        if Ls > N_POS or T > N_POS:
+            raise ValueError(f"widths ({Ls}, {T}): the regenerator's position table has {N_POS} rows")
+        n = len(pairs)
+        src = torch.zeros(n, Ls, dtype=torch.int64)
+        tgt = torch.zeros(n, T + 1, dtype=torch.int64)
+        for i in range(n):
+            src[i, :len(srcs[i])] = torch.tensor(srcs[i])
+            tgt[i, :len(tgts[i])] = torch.tensor(tgts[i])
+        if n and (int(min(src.min(), tgt.min())) < 0 or int(max(src.max(), tgt.max())) >= self.n_rows):
+            raise IndexError(f"ids outside [0, {self.n_rows})")
+        return (src, torch.tensor([len(s) for s in srcs], dtype=torch.int64), tgt,
+                torch.tensor([len(t) for t in tgts], dtype=torch.int64), Ls, T)
 
-def random_state_dict(n_item: int = NUM_ITEM["toy"], K: int = 5, seed: int = 0, std: float = 0.1):
+    def _params_as(self, dtype, device):
+        key = (dtype, str(device))
+        if key not in self._cast:
+            self._cast[key] = {k: v.to(device=device, dtype=dtype) for k, v in self.p.items()}
+        return self._cast[key]
+
+    def _score_torch(self, src, tgt, tgt_len, w, want_cond, causal_source, dtype):
+        """Generator.forward + cross_entropy(reduction='none') of 2.Pretrain_regenerator.py in eval mode, batched, from the named
+        parameters: (nll [n_w, n, T] or None when w is None, condition logits [n, K] or None)"""
+        dev = src.device
+        p = self._params_as(dtype, dev)
+        E, P = p["item_embedding.weight"], p["position_embedding.weight"]
+        n, Ls = src.shape
+        T = tgt.shape[1] - 1
+        tgt_in, tgt_out = tgt[:, :-1], tgt[:, 1:]
+        ninf = float("-inf")
+
+        def mha(pre, xq, xkv, bias):
+            W, b = p[pre + ".in_proj_weight"], p[pre + ".in_proj_bias"]
+            B, Lq, _ = xq.shape
+            Lk = xkv.shape[1]
+            q = F.linear(xq, W[:D], b[:D]).view(B, Lq, H, D // H).transpose(1, 2)
+            k = F.linear(xkv, W[D:2 * D], b[D:2 * D]).view(B, Lk, H, D // H).transpose(1, 2)
+            v = F.linear(xkv, W[2 * D:], b[2 * D:]).view(B, Lk, H, D // H).transpose(1, 2)
+            a = torch.softmax((q @ k.transpose(-1, -2)) / math.sqrt(D // H) + bias, -1)
+            return F.linear((a @ v).transpose(1, 2).reshape(B, Lq, D), p[pre + ".out_proj.weight"], p[pre + ".out_proj.bias"])
+
+        def ln(x, pre):
+            return F.layer_norm(x, (D,), p[pre + ".weight"], p[pre + ".bias"], LN_EPS)
+
+        def ffn(x, pre):
+            return F.linear(F.gelu(F.linear(x, p[pre + ".linear1.weight"], p[pre + ".linear1.bias"])),
+                            p[pre + ".linear2.weight"], p[pre + ".linear2.bias"])
+
+        def enc_layers(x, bias, stem):
+            for i in range(N_LAYER):
+                pre = f"{stem}.layers.{i}"
+                x = ln(x + mha(pre + ".self_attn", x, x, bias), pre + ".norm1")
+                x = ln(x + ffn(x, pre), pre + ".norm2")
+            return x
+
+        def key_bias(ids):
+            return torch.zeros(ids.shape, dtype=dtype, device=dev).masked_fill(ids == 0, ninf)[:, None, None, :]
+
+        def causal(L):
+            return torch.full((L, L), ninf, dtype=dtype, device=dev).triu(1)
+
+        tgt_kb = key_bias(tgt_in)
+        x_t = E[tgt_in] + P[:T]
+        cond = None
+        if want_cond:
+            y = enc_layers(x_t, causal(T) + tgt_kb, "condition_encoder.encoder")
+            keep = torch.arange(T, device=dev)[None, :] < tgt_len[:, None]
+            pooled = (y * keep[:, :, None].to(dtype)).sum(1) / tgt_len[:, None].to(dtype)
+            hid = torch.relu(F.linear(pooled, p["condition_encoder.condition_layer.0.weight"], p["condition_encoder.condition_layer.0.bias"]))
+            cond = F.linear(hid, p["condition_encoder.condition_layer.2.weight"], p["condition_encoder.condition_layer.2.bias"])
+        if w is None:
+            return None, cond
+        src_kb = key_bias(src)
+        x = enc_layers(E[src] + P[:Ls], (causal(Ls) if causal_source else 0) + src_kb, "transformer.encoder")
+        mem = ln(x, "transformer.encoder.norm")
+        c1 = torch.relu(F.linear(mem, p["condition_linear.0.weight"], p["condition_linear.0.bias"]))
+        mem = F.linear(c1, p["condition_linear.2.weight"], p["condition_linear.2.bias"]).view(n, Ls, self.K, D)
+        dup = ((src[:, :, None] == src[:, None, :]) & torch.ones(Ls, Ls, dtype=torch.bool, device=dev).tril(-1)).any(-1)   # id seen earlier
+        Es = E[src]                                                           # the only table rows the masked logits keep
+        hit = (tgt_out[:, :, None] == src[:, None, :]) & ~dup[:, None, :]     # [n, T, Ls]: the slot of the target id, if any
+        dec_bias = causal(T) + tgt_kb
+        out = []
+        for wi in w.to(device=dev, dtype=dtype):
+            mc = (mem * wi[:, None, :, None]).sum(-2)
+            h = x_t
+            for i in range(N_LAYER):
+                pre = f"transformer.decoder.layers.{i}"
+                h = ln(h + mha(pre + ".self_attn", h, h, dec_bias), pre + ".norm1")
+                h = ln(h + mha(pre + ".multihead_attn", h, mc, src_kb), pre + ".norm2")
+                h = ln(h + ffn(h, pre), pre + ".norm3")
+            h = ln(h, "transformer.decoder.norm")
+            lg = (h @ Es.transpose(1, 2)).masked_fill(dup[:, None, :], ninf)
+            lse = torch.logsumexp(lg, -1)
+            tl = torch.where(hit, lg, torch.zeros((), dtype=dtype, device=dev)).sum(-1)
+            nll = torch.where(hit.any(-1), lse - tl, torch.full((), float("inf"), dtype=dtype, device=dev))
+            out.append(nll.masked_fill(tgt_out == 0, 0.0))
+        return torch.stack(out), cond
+
+    def score_device(self, src, src_len, tgt, tgt_len, w, causal_source=True, workspace=None):
+        """the HIP call on device tensors (src [n, Ls], tgt [n, T + 1] int64, w [n_w, n, K] fp32): nll [n_w, n, T] on the device.
+        Only enqueues on the current stream (capturable); `workspace` may be reused between calls of the same sizes"""
+        lib = _lib.load()
+        plan = self.score_plan()
+        n, Ls = src.shape
+        T = tgt.shape[1] - 1
+        n_w = w.shape[0]
+        nb = lib.dr4sr_regen_score_workspace_bytes(C.byref(plan), n, Ls, T, n_w)
+        if nb < 0:
+            _lib.check(int(nb), "dr4sr_regen_score_workspace_bytes")
+        if workspace is None:
+            workspace = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
+        nll = torch.empty(n_w, n, T, dtype=torch.float32, device=self.device)
+        _lib.check(lib.dr4sr_regen_score(C.byref(plan), _lib.ptr(src), _lib.ptr(src_len), _lib.ptr(tgt), _lib.ptr(tgt_len), n, Ls, T,
+                                         _lib.ptr(w), n_w, int(bool(causal_source)), C.c_void_p(workspace.data_ptr()), workspace.numel(),
+                                         _lib.ptr(nll), _lib.cur_stream()), "dr4sr_regen_score")
+        return nll
+
+    def condition_device(self, tgt, tgt_len, workspace=None):
+        """condition logits [n, K] of the condition_encoder on device tensors (HIP; only enqueues)"""
+        lib = _lib.load()
+        plan = self.score_plan()
+        n, T = tgt.shape[0], tgt.shape[1] - 1
+        nb = lib.dr4sr_regen_score_workspace_bytes(C.byref(plan), n, 1, T, 1)
+        if nb < 0:
+            _lib.check(int(nb), "dr4sr_regen_score_workspace_bytes")
+        if workspace is None:
+            workspace = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
+        out = torch.empty(n, self.K, dtype=torch.float32, device=self.device)
+        _lib.check(lib.dr4sr_regen_score_condition(C.byref(plan), _lib.ptr(tgt), _lib.ptr(tgt_len), n, T, C.c_void_p(workspace.data_ptr()),
+                                                   workspace.numel(), _lib.ptr(out), _lib.cur_stream()), "dr4sr_regen_score_condition")
+        return out
+
+    @torch.no_grad()
+    def score(self, pairs, conditions="all", causal_source: bool = True, width=None, backend: str = "hip", dtype=torch.float32):
+        """Teacher-forced per-token NLL of every (sequence, pattern) pair — the forward and loss of 2.Pretrain_regenerator.py's
+        train_epoch in eval mode.  conditions: "all" (each of the K one-hot condition weights, the memory slices stage 3 decodes
+        with), "encoder" (softmax of the condition_encoder's logits: training's weights without the Gumbel noise, tau = 1) or a
+        [n_w, n_pair, K] tensor used as is.  causal_source=False scores with the bidirectional source encoder of stage 3.
+        width=(Ls, T) scores at those matrix widths (a slice of a file scores as inside the file).  `dtype` applies to
+        backend="torch" only."""
+        if backend not in ("hip", "torch"):
+            raise ValueError(f"backend must be 'hip' or 'torch', not {backend!r}")
+        src, src_len, tgt, tgt_len, Ls, T = self._pack_pairs(pairs, width)
+        n = len(pairs)
+        if isinstance(conditions, str):
+            if conditions not in ("all", "encoder"):
+                raise ValueError(f"conditions must be 'all', 'encoder' or a [n_w, n_pair, K] tensor, not {conditions!r}")
+            if conditions == "encoder" and not self.has_condition_encoder:
+                raise ValueError("conditions='encoder' needs condition_encoder.* and this state dict has none")
+            w = torch.eye(self.K)[:, None, :].expand(self.K, n, self.K) if conditions == "all" else None
+        else:
+            w = torch.as_tensor(conditions)
+            if tuple(w.shape[1:]) != (n, self.K) or w.dim() != 3:
+                raise ValueError(f"condition weights of shape {tuple(w.shape)}, expected [n_w, {n}, {self.K}]")
+        hip = backend == "hip"
+        odt = torch.float32 if hip else dtype
+        dev = self.device
+        nll, cond = [], []
+        for a in range(0, n, PAIRS_PER_CALL if hip else ROWS_PER_TORCH):
+            b = min(n, a + (PAIRS_PER_CALL if hip else ROWS_PER_TORCH))
+            s_d, t_d, tl_d = src[a:b].to(dev).contiguous(), tgt[a:b].to(dev).contiguous(), tgt_len[a:b].to(dev).contiguous()
+            wc = None if w is None else w[:, a:b]
+            if hip:
+                c = self.condition_device(t_d, tl_d) if self.has_condition_encoder else None
+                if wc is None:
+                    wc = torch.softmax(c, -1)[None]
+                wc = wc.to(dev, torch.float32).contiguous()
+                x = self.score_device(s_d, src_len[a:b].to(dev).contiguous(), t_d, tl_d, wc, causal_source)
+            else:
+                c = None
+                if wc is None:
+                    _, c = self._score_torch(s_d, t_d, tl_d, None, True, causal_source, dtype)
+                    wc = torch.softmax(c, -1)[None]
+                x, c2 = self._score_torch(s_d, t_d, tl_d, wc, self.has_condition_encoder and c is None, causal_source, dtype)
+                c = c2 if c is None else c
+            nll.append(x.cpu())
+            if c is not None:
+                cond.append(c.cpu())
+        n_w = 1 if w is None else w.shape[0]
+        nll = torch.cat(nll, 1) if nll else torch.zeros(n_w, 0, T, dtype=odt)
+        return ScoreResult(nll, (tgt[:, 1:] != 0).sum(1), torch.cat(cond) if cond else None, Ls, T)
+
+
+class ScoreResult:
+    """RegenModel.score's result: nll [n_w, n_pair, T] (0 where tgt_out is PAD, +inf where the target id is not in the source),
+    n_tok [n_pair], cond_logits [n_pair, K] or None, and the widths (Ls, T) the pairs were scored at"""
+
+    def __init__(self, nll, n_tok, cond_logits, Ls, T):
+        self.nll, self.n_tok, self.cond_logits, self.width = nll, n_tok, cond_logits, (Ls, T)
+
+    def per_pair(self):
+        """[n_w, n_pair] float64: each pair's summed NLL (its negative log-likelihood under each condition weight)"""
+        return self.nll.double().sum(-1)
+
+    def loss(self):
+        """[n_w] float64: nn.CrossEntropyLoss(ignore_index=0) of the reference over ALL given pairs as one batch (sum of the token
+        NLLs over the token count), summed in float64 on the host"""
+        return self.per_pair().sum(-1) / max(int(self.n_tok.sum()), 1)
+
+
+def random_state_dict(n_item: int = NUM_ITEM["toy"], K: int = 5, seed: int = 0, std: float = 0.1, condition_encoder: bool = False):
     """a seeded random regenerator state dict in the reference's names (normal weights, LayerNorm weight 1 / bias 0): the
     measurement's worst case (no row stops early) and the synthetic cross-checks' model"""
     g = torch.Generator().manual_seed(seed)
@@ -320,6 +576,12 @@ def random_state_dict(n_item: int = NUM_ITEM["toy"], K: int = 5, seed: int = 0, 
         else:
             sd[name] = std * torch.randn(shape, generator=g)
     sd["item_embedding_decoder.weight"] = sd["item_embedding.weight"]
+    if condition_encoder:      # drawn after everything else: the tensors above do not depend on this flag
+        for name, shape in list(zip(score_param_names(), score_param_shapes(n_item + 2, K)))[len(param_names()):]:
+            if name.split(".")[-2].startswith("norm"):
+                sd[name] = torch.ones(shape) if name.endswith("weight") else torch.zeros(shape)
+            else:
+                sd[name] = std * torch.randn(shape, generator=g)
     return sd
 
 
@@ -365,14 +627,54 @@ def hybrid_inference(root_path: str, ckpt_name: str = "regenerator.pth", begin: 
     return out_path
 
 
+def score_file(root_path: str, pairs_file: str = "seq-pat-pair.pth", ckpt_name: str = "regenerator.pth", begin: int = 0, end: int = 1000000,
+               causal_source: bool = True, backend: str = "hip", device="cuda"):
+    """the --score report: teacher-forced loss of the pairs begin*5000 : end*5000 of a pairs file, scored at the widths of the whole
+    file, under each one-hot condition and under the condition_encoder's own softmax"""
+    parts = root_path.split("/")
+    dataset = parts[-2] if len(parts) >= 2 else None
+    model = RegenModel.from_state_dict(torch.load(os.path.join(root_path, ckpt_name), map_location="cpu"), device, dataset=dataset)
+    pairs = torch.load(os.path.join(root_path, pairs_file))
+    width = model._pack_pairs(pairs, None)[4:]
+    pairs = pairs[begin * 5000:end * 5000]
+    res = model.score(pairs, "all", causal_source, width, backend)
+    per = res.per_pair()                                         # [K, n]
+    n_tok = max(int(res.n_tok.sum()), 1)
+    best = per.argmin(0)
+    rep = {"pairs": len(pairs), "tokens": int(res.n_tok.sum()), "width": list(width), "causal_source": bool(causal_source),
+           "inf_tokens": int(torch.isinf(res.nll).sum()),
+           "loss_encoder": None, "loss_best_condition": float(per.min(0).values.sum() / n_tok),
+           "nll_per_condition": [float(v) for v in res.loss()],
+           "argmin_hist": torch.bincount(best, minlength=model.K).tolist(),
+           "encoder_argmax_hist": None, "agreement": None}
+    if model.has_condition_encoder and res.cond_logits is not None:
+        rep["loss_encoder"] = float(model.score(pairs, "encoder", causal_source, width, backend).loss()[0])
+        top = res.cond_logits.argmax(-1)
+        rep["encoder_argmax_hist"] = torch.bincount(top, minlength=model.K).tolist()
+        rep["agreement"] = float((top == best).double().mean()) if len(pairs) else None
+    return rep
+
+
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="DR4SR stage 3: regenerate train_regen.pth with the pre-trained regenerator")
+    ap = argparse.ArgumentParser(description="DR4SR stage 3: regenerate train_regen.pth with the pre-trained regenerator; "
+                                             "--score: teacher-forced loss of a regenerator on a pairs file instead")
     ap.add_argument("--root_path", type=str, default="./dataset/amazon-toys/toy/", help="The path to the dataset.")
     ap.add_argument("--ckpt_name", type=str, default="regenerator.pth", help="The name of pretrained regenerator")
     ap.add_argument("--begin", "-b", type=int, default=0, help="Used for multi-processing. Beginning of the inference.")
     ap.add_argument("--end", "-e", type=int, default=1000000, help="Used for multi-processing. End of the inference.")
     ap.add_argument("--gpu", type=int, default=0)
+    ap.add_argument("--score", action="store_true", help="print one JSON line of teacher-forced losses instead of decoding")
+    ap.add_argument("--pairs_file", type=str, default="seq-pat-pair.pth", help="--score: the pairs file under root_path")
+    ap.add_argument("--bidirectional_source", action="store_true", help="--score: stage 3's source encoder mask instead of stage 2's")
+    ap.add_argument("--backend", choices=("hip", "torch"), default="hip", help="--score: 'torch' is the eager cross-check (runs on --device)")
+    ap.add_argument("--device", type=str, default=None, help="--score with --backend torch: e.g. cpu")
     a = ap.parse_args(argv)
+    if a.score:
+        dev = a.device or f"cuda:{a.gpu}"
+        if a.backend == "hip" or dev.startswith("cuda"):
+            torch.cuda.set_device(a.gpu)
+        print(json.dumps(score_file(a.root_path, a.pairs_file, a.ckpt_name, a.begin, a.end, not a.bidirectional_source, a.backend, dev)))
+        return
     torch.cuda.set_device(a.gpu)
     path = hybrid_inference(a.root_path, a.ckpt_name, a.begin, a.end, "hip", torch.device("cuda", a.gpu))
     print(path)

@@ -658,6 +658,46 @@ int dr4sr_pairs_match(const int32_t* seqs, const int32_t* seq_len, int64_t n_seq
                       const int64_t* pat_off, int64_t n_pat, int64_t n_ids, uint64_t seed, int64_t seq_index0, int64_t pat_index0,
                       int32_t n_chunks, void* workspace, int64_t workspace_bytes, int32_t* n_match, int32_t* chosen, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Teacher-forced scoring of the regenerator (the forward and loss of DR4SR stage 2, the reference's 2.Pretrain_regenerator.py
+ * Generator.forward + CrossEntropyLoss(ignore_index = 0) in eval mode: dropout off), csrc/regen_score.hip.  Additive to ABI 10.
+ * A pair is (sequence s, pattern t); src row = [SOS] + s + [EOS], tgt row = [SOS] + t + [EOS], both padded with 0 to the widths of the
+ * whole pairs file: src [n_pair, Ls], tgt [n_pair, T + 1] (tgt_in = columns 0..T-1, tgt_out = columns 1..T), src_len / tgt_len [n_pair]
+ * int64 = len(s) + 2 / len(t) + 2.  Unlike the decode entry points, the PAD entries of a src row are read: they are masked as attention
+ * keys and PAD 0 is one of the ids the softmax runs over when the row is padded (the reference's condition_mask).
+ *   source    : E[src] + P[0:Ls] -> 2 encoder layers, causal (causal_source != 0: what stage 2 trains with) or bidirectional (what stage
+ *               3 decodes with), keys with id 0 masked -> encoder.norm -> condition_linear -> memory[Ls, K, 64]
+ *   condition : condition_encoder = 2 causal encoder layers over E[tgt_in] + P[0:T] (no final norm) -> sum of the first min(tgt_len, T)
+ *               outputs divided by tgt_len (a row that fills the width has lost its EOS column and still divides by tgt_len) ->
+ *               Linear 64 -> 64, ReLU, Linear 64 -> K: cond_logits [n_pair, K]
+ *   score     : memory_cond = sum_k w[k] memory[:, k] for a weight vector w[K] (one-hot: the slice stage 3 decodes with; training feeds
+ *               gumbel_softmax(cond_logits)) -> 2 decoder layers over E[tgt_in] + P[0:T] (causal, keys with id 0 masked; cross-attention
+ *               over memory_cond, keys with src id 0 masked) -> decoder.norm -> logits h . E[id] over the DISTINCT ids of the padded src
+ *               row only -> nll[t] = logsumexp - logit[tgt_out[t]]; 0 where tgt_out[t] = 0; +inf where tgt_out[t] is not in the src row.
+ * w [n_w, n_pair, K] fp32, nll [n_w, n_pair, T] fp32 (every entry is written).  The source side runs once per pair for all n_w weight
+ * vectors.  A pair's values do not depend on n_pair, n_w, its index or the other pairs (bit-identical alone or batched); no atomics.
+ * Parameters: the DR4SR_REGEN_TENSORS tensors of the decode layout at the same indices and offsets, then
+ *   per condition-encoder layer i, [70+12*i+j]: condition_encoder.encoder.layers.{i}. with the 12 tensors of an encoder layer above
+ *   [94] condition_encoder.condition_layer.0.weight[D,D]  [95] .0.bias[D]  [96] .2.weight[K,D]  [97] .2.bias[K]
+ * (all zero for a model saved without them: only the condition call reads them).  The plan is a dr4sr_regen_plan whose params / n_params
+ * are THIS layout's buffer and size (max_len is not used); a buffer of the 70-tensor layout is refused with DR4SR_E_ARG.
+ * Checked on the host before anything is launched: the plan (as for decode), null pointers, n_pair < 0 or >= 2^24, n_w < 1,
+ * n_pair * n_w * T >= 2^30, Ls < 1, T < 1 (DR4SR_E_ARG); Ls > 50 or T > 50, the position table (DR4SR_E_SHAPE); a null or too small
+ * workspace (DR4SR_E_WS).  Ids are clamped to [0, n_rows) and the lengths to their widths on the device.  Everything is enqueued on
+ * `stream` (capturable); the workspace needs no initialisation and may be reused by any later call. */
+#define DR4SR_REGEN_SCORE_TENSORS 98
+/* fills offsets[0..DR4SR_REGEN_SCORE_TENSORS) (may be NULL); returns n_params, or DR4SR_E_ARG for n_rows < 3 / K < 1 */
+int64_t dr4sr_regen_score_param_layout(int32_t n_rows, int32_t K, int64_t* offsets);
+/* bytes of scratch: 4 (n_pair + 1) rounded up to 256, plus n_pair * K * 2 * Ls * 128 floats (the cross-attention K | V of every
+ * condition, both decoder layers: 256 KB per pair at Ls = 50, K = 5); the same for every n_w.  The condition call needs the first term
+ * only: the size for Ls = 1 is always enough for it. */
+int64_t dr4sr_regen_score_workspace_bytes(const dr4sr_regen_plan* plan, int64_t n_pair, int32_t Ls, int32_t T, int32_t n_w);
+int dr4sr_regen_score_condition(const dr4sr_regen_plan* plan, const int64_t* tgt, const int64_t* tgt_len, int64_t n_pair, int32_t T,
+                                void* workspace, int64_t workspace_bytes, float* cond_logits, void* stream);
+int dr4sr_regen_score(const dr4sr_regen_plan* plan, const int64_t* src, const int64_t* src_len, const int64_t* tgt, const int64_t* tgt_len,
+                      int64_t n_pair, int32_t Ls, int32_t T, const float* w, int32_t n_w, int32_t causal_source, void* workspace,
+                      int64_t workspace_bytes, float* nll, void* stream);
+
 /* Test / measurement hooks (dr4sr_dropout_mask, dr4sr_*_launch_kernel) are NOT part of this product surface: they are declared in
  * include/dr4sr_hip_hooks.h, and nothing under dr4sr_amd/ calls them. */
 
