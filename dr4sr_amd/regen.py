@@ -30,6 +30,8 @@ NUM_ITEM = {"toy": 11925, "sport": 18358, "beauty": 12102, "yelp": 20034}     # 
 ROWS_PER_CALL = 16384          # decode rows per HIP call: ~1.3 GB of workspace (csrc/regen.hip, about 77 KB per row)
 ROWS_PER_TORCH = 2048          # decode rows per torch batch ([rows, n_rows] logits)
 PAIRS_PER_CALL = 4096          # score(): pairs per HIP call (csrc/regen_score.hip keeps K x 2 x Ls x 128 floats per pair: 256 KB at Ls = 50)
+SCORE_BWD_PAIRS_PER_CALL = 256 # loss_and_grad(): pairs per HIP call (the backward keeps ~2 MB of records per pair at Ls = 50: ~0.6 GB)
+COND_BWD_PAIRS_PER_CALL = 1024 # condition_grad(): pairs per HIP call (csrc/regen_score_bwd.hip keeps ~16 KB per token slot: ~0.5 GB at T = 19)
 MAX_SEQ_LEN = 50
 
 _ENC = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias",
@@ -385,11 +387,12 @@ class RegenModel:
             self._cast[key] = {k: v.to(device=device, dtype=dtype) for k, v in self.p.items()}
         return self._cast[key]
 
-    def _score_torch(self, src, tgt, tgt_len, w, want_cond, causal_source, dtype):
+    def _score_torch(self, src, tgt, tgt_len, w, want_cond, causal_source, dtype, params=None):
         """Generator.forward + cross_entropy(reduction='none') of 2.Pretrain_regenerator.py in eval mode, batched, from the named
-        parameters: (nll [n_w, n, T] or None when w is None, condition logits [n, K] or None)"""
+        parameters: (nll [n_w, n, T] or None when w is None, condition logits [n, K] or None).  `params` (name -> tensor of `dtype` on
+        src's device) replaces the model's own: loss_and_grad passes leaves that require grad"""
         dev = src.device
-        p = self._params_as(dtype, dev)
+        p = self._params_as(dtype, dev) if params is None else params
         E, P = p["item_embedding.weight"], p["position_embedding.weight"]
         n, Ls = src.shape
         T = tgt.shape[1] - 1
@@ -497,6 +500,244 @@ class RegenModel:
                                                    workspace.numel(), _lib.ptr(out), _lib.cur_stream()), "dr4sr_regen_score_condition")
         return out
 
+    # ------------------------------------------------------------------------------------------------ parameters in and out
+    def state_dict(self):
+        """the model's parameters by their state-dict names (fp32 clones on the model's device); item_embedding_decoder.weight is the
+        same table as item_embedding.weight, as the reference ties them"""
+        sd = {k: v.clone() for k, v in self.p.items()}
+        sd["item_embedding_decoder.weight"] = sd["item_embedding.weight"]
+        return sd
+
+    @torch.no_grad()
+    def load_params(self, params: dict):
+        """overwrite parameters IN PLACE: self.p, the dtype casts and both flat buffers keep their device addresses, so plans, views
+        and captured graphs stay valid.  `params` maps state-dict names to tensors of the stored shapes (a subset is allowed)"""
+        for name, v in params.items():
+            if name == "item_embedding_decoder.weight":
+                continue
+            if name not in self.p:
+                raise KeyError(f"{name} is not a parameter of this model")
+            if tuple(v.shape) != tuple(self.p[name].shape):
+                raise ValueError(f"{name}: shape {tuple(v.shape)}, expected {tuple(self.p[name].shape)}")
+        for name, v in params.items():
+            if name == "item_embedding_decoder.weight":
+                continue
+            self.p[name].copy_(v.detach().to(self.device, torch.float32))
+            for cast in self._cast.values():
+                cast[name].copy_(self.p[name].to(device=cast[name].device, dtype=cast[name].dtype))
+        for buf, names, fn, cnt in ((self._flat, param_names(), "dr4sr_regen_param_layout", _lib.REGEN_TENSORS),
+                                    (self._score_flat, score_param_names(), "dr4sr_regen_score_param_layout", _lib.REGEN_SCORE_TENSORS)):
+            if buf is None:
+                continue
+            off = (C.c_int64 * cnt)()
+            getattr(_lib.load(), fn)(self.n_rows, self.K, off)
+            for i, name in enumerate(names):
+                if name in params:
+                    buf[off[i]:off[i] + self.p[name].numel()] = self.p[name].reshape(-1)
+
+    # ------------------------------------------------------------------------------------------------ gradients
+    def grads_from_flat(self, flat):
+        """views of a flat gradient buffer in the 98-tensor score layout, by state-dict name (70 names without a condition encoder)"""
+        off = (C.c_int64 * _lib.REGEN_SCORE_TENSORS)()
+        _lib.load().dr4sr_regen_score_param_layout(self.n_rows, self.K, off)
+        out = {}
+        for i, (name, shape) in enumerate(zip(score_param_names(), score_param_shapes(self.n_rows, self.K))):
+            if name in self.p:
+                out[name] = flat[off[i]:off[i] + math.prod(shape)].view(shape)
+        return out
+
+    def condition_bwd_device(self, tgt, tgt_len, dlogits, grad=None, accumulate=False, workspace=None):
+        """the HIP backward of condition_device on device tensors: dlogits [n, K] fp32 -> the flat gradient (98-tensor score layout;
+        condition_encoder.* and the two tables receive values).  accumulate=False overwrites every element of `grad` (a new buffer
+        when None), True adds to it.  Only enqueues on the current stream (capturable); the same inputs give the same bits"""
+        lib = _lib.load()
+        plan = self.score_plan()
+        n, T = tgt.shape[0], tgt.shape[1] - 1
+        nb = lib.dr4sr_regen_score_condition_bwd_workspace_bytes(C.byref(plan), n, T)
+        if nb < 0:
+            _lib.check(int(nb), "dr4sr_regen_score_condition_bwd_workspace_bytes")
+        if workspace is None:
+            workspace = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
+        if grad is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs the gradient buffer to add to")
+            grad = torch.empty(plan.n_params, dtype=torch.float32, device=self.device)
+        if grad.numel() != plan.n_params or grad.dtype != torch.float32:
+            raise ValueError(f"grad must hold {plan.n_params} fp32 values")
+        _lib.check(lib.dr4sr_regen_score_condition_bwd(C.byref(plan), _lib.ptr(tgt), _lib.ptr(tgt_len), n, T, _lib.ptr(dlogits),
+                                                       C.c_void_p(workspace.data_ptr()), workspace.numel(), _lib.ptr(grad),
+                                                       int(bool(accumulate)), _lib.cur_stream()), "dr4sr_regen_score_condition_bwd")
+        return grad
+
+    def score_bwd_device(self, src, src_len, tgt, tgt_len, w, dnll, causal_source=True, grad=None, accumulate=False, workspace=None):
+        """the HIP backward of score_device on device tensors: dnll [n_w, n, T] fp32 -> (flat gradient in the 98-tensor score layout,
+        dw [n_w, n, K], nll [n_w, n, T]).  Self-contained (runs the forward it needs); accumulate=False overwrites every element of
+        `grad` (a new buffer when None), True adds.  Only enqueues on the current stream; the same inputs give the same bits"""
+        lib = _lib.load()
+        plan = self.score_plan()
+        n, Ls = src.shape
+        T = tgt.shape[1] - 1
+        n_w = w.shape[0]
+        nb = lib.dr4sr_regen_score_bwd_workspace_bytes(C.byref(plan), n, Ls, T, n_w)
+        if nb < 0:
+            _lib.check(int(nb), "dr4sr_regen_score_bwd_workspace_bytes")
+        if workspace is None:
+            workspace = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
+        if grad is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs the gradient buffer to add to")
+            grad = torch.empty(plan.n_params, dtype=torch.float32, device=self.device)
+        if grad.numel() != plan.n_params or grad.dtype != torch.float32:
+            raise ValueError(f"grad must hold {plan.n_params} fp32 values")
+        if tuple(dnll.shape) != (n_w, n, T):
+            raise ValueError(f"dnll of shape {tuple(dnll.shape)}, expected ({n_w}, {n}, {T})")
+        dw = torch.empty(n_w, n, self.K, dtype=torch.float32, device=self.device)
+        nll = torch.empty(n_w, n, T, dtype=torch.float32, device=self.device)
+        _lib.check(lib.dr4sr_regen_score_bwd(C.byref(plan), _lib.ptr(src), _lib.ptr(src_len), _lib.ptr(tgt), _lib.ptr(tgt_len), n, Ls, T,
+                                             _lib.ptr(w), n_w, int(bool(causal_source)), _lib.ptr(dnll), C.c_void_p(workspace.data_ptr()),
+                                             workspace.numel(), _lib.ptr(grad), _lib.ptr(dw), _lib.ptr(nll), int(bool(accumulate)),
+                                             _lib.cur_stream()), "dr4sr_regen_score_bwd")
+        return grad, dw, nll
+
+    def _loss_and_grad_hip(self, src, src_len, tgt, tgt_len, T, conditions, causal_source, noise, tau, entropy_weight):
+        dev = self.device
+        n = src.shape[0]
+        encoder = isinstance(conditions, str)
+        n_tok = max(int((tgt[:, 1:] != 0).sum()), 1)
+        flat = None
+        loss = torch.zeros((), dtype=torch.float64)
+        entropy = torch.zeros((), dtype=torch.float64)
+        dws, conds = [], []
+        for a in range(0, n, SCORE_BWD_PAIRS_PER_CALL):
+            b = min(n, a + SCORE_BWD_PAIRS_PER_CALL)
+            s_d, sl_d = src[a:b].to(dev).contiguous(), src_len[a:b].to(dev).contiguous()
+            t_d, tl_d = tgt[a:b].to(dev).contiguous(), tgt_len[a:b].to(dev).contiguous()
+            c = self.condition_device(t_d, tl_d) if self.has_condition_encoder else None
+            if encoder:                  # the few [n, K] operations between dw and the condition encoder's backward: torch autograd
+                c_leaf = c.detach().requires_grad_(True)
+                z = c_leaf if noise is None else c_leaf + torch.as_tensor(noise)[a:b].to(dev, torch.float32)
+                w0 = torch.softmax(z / tau, -1)
+                ent = -(w0 * torch.log(w0 + 1e-12)).sum(-1).sum() / n
+                w = w0.detach()[None].contiguous()
+            else:
+                w = conditions[:, a:b].to(dev, torch.float32).contiguous()
+            dnll = torch.full((w.shape[0], b - a, T), 1.0 / n_tok, dtype=torch.float32, device=dev)
+            flat, dw, nll = self.score_bwd_device(s_d, sl_d, t_d, tl_d, w, dnll, causal_source, flat, accumulate=flat is not None)
+            loss += float(nll.double().sum()) / n_tok
+            if encoder:
+                entropy += float(ent.detach())
+                (dlog,) = torch.autograd.grad((w0 * dw[0]).sum() + entropy_weight * ent, c_leaf)
+                self.condition_bwd_device(t_d, tl_d, dlog.contiguous(), flat, accumulate=True)
+            dws.append(dw)
+            if c is not None:
+                conds.append(c)
+        n_w = 1 if encoder else conditions.shape[0]
+        if flat is None:
+            flat = torch.zeros(self.score_flat().numel(), dtype=torch.float32, device=dev)
+        return GradResult(loss, entropy if encoder else None, self.grads_from_flat(flat),
+                          torch.cat(dws, 1) if dws else torch.zeros(n_w, 0, self.K, device=dev), torch.cat(conds) if conds else None)
+
+    def condition_grad(self, pairs, dlogits, width=None, backend: str = "hip", dtype=torch.float32):
+        """gradients of sum(cond_logits * dlogits) over the given pairs: state-dict name -> tensor for condition_encoder.* and the
+        two tables (the vector-Jacobian product of score()'s cond_logits).  backend="hip" runs csrc/regen_score_bwd.hip, chunked
+        with `accumulate`; backend="torch" is autograd through the eager restatement in `dtype`"""
+        if backend not in ("hip", "torch"):
+            raise ValueError(f"backend must be 'hip' or 'torch', not {backend!r}")
+        if not self.has_condition_encoder:
+            raise ValueError("condition_grad needs condition_encoder.* and this state dict has none")
+        _, _, tgt, tgt_len, _, T = self._pack_pairs(pairs, width)
+        n = len(pairs)
+        dlogits = torch.as_tensor(dlogits)
+        if tuple(dlogits.shape) != (n, self.K):
+            raise ValueError(f"dlogits of shape {tuple(dlogits.shape)}, expected ({n}, {self.K})")
+        dev = self.device
+        names = ["item_embedding.weight", "position_embedding.weight"] + [k for k in score_param_names() if k.startswith("condition_encoder.")]
+        if backend == "hip":
+            flat = None
+            for a in range(0, max(n, 1), COND_BWD_PAIRS_PER_CALL):
+                b = min(n, a + COND_BWD_PAIRS_PER_CALL)
+                flat = self.condition_bwd_device(tgt[a:b].to(dev).contiguous(), tgt_len[a:b].to(dev).contiguous(),
+                                                 dlogits[a:b].to(dev, torch.float32).contiguous(), flat, accumulate=flat is not None)
+            g = self.grads_from_flat(flat)
+            return {k: g[k] for k in names}
+        leaves = {k: v.to(device=dev, dtype=dtype).clone().requires_grad_(k in names) for k, v in self.p.items()}
+        for a in range(0, n, ROWS_PER_TORCH):
+            b = min(n, a + ROWS_PER_TORCH)
+            _, c = self._score_torch(tgt[a:b, :1].to(dev), tgt[a:b].to(dev), tgt_len[a:b].to(dev), None, True, True, dtype, leaves)
+            (c * dlogits[a:b].to(dev, dtype)).sum().backward()
+        return {k: (leaves[k].grad if leaves[k].grad is not None else torch.zeros_like(leaves[k])) for k in names}
+
+    def loss_and_grad(self, pairs, conditions, causal_source: bool = True, width=None, backend: str = "hip", dtype=torch.float32,
+                      noise=None, tau: float = 1.0, entropy_weight: float = 0.0):
+        """The reference's training loss in eval mode and its gradient with respect to every parameter.
+
+        loss: CrossEntropyLoss(ignore_index=0) over ALL given pairs as one batch, per weight vector and summed over them.
+        conditions: a [n_w, n, K] tensor (a constant; `dw` is the loss's gradient with respect to it) or "encoder":
+        w = softmax((cond_logits + noise) / tau), F.gumbel_softmax's soft sample for recorded noise (zero when None), and the
+        differentiated scalar is CE + entropy_weight * (-(w log(w + 1e-12)).sum(-1).mean()); the reference uses weight 1.
+        A target id outside its source makes the reference's loss inf: ValueError here.
+
+        backend="hip": csrc/regen_score_bwd.hip, chunked at SCORE_BWD_PAIRS_PER_CALL pairs with `accumulate`; in "encoder" mode the
+        few [n, K] operations between dw and the condition encoder's backward run in torch autograd on the device.
+        backend="torch": autograd through the eager restatement, fp32 or fp64 (`dtype`): the float64 side of every check."""
+        if backend not in ("hip", "torch"):
+            raise ValueError(f"backend must be 'hip' or 'torch', not {backend!r}")
+        src, src_len, tgt, tgt_len, Ls, T = self._pack_pairs(pairs, width)
+        n = len(pairs)
+        for i in range(n):
+            have = set(src[i].tolist())
+            if any(int(v) not in have for v in tgt[i, 1:int(tgt_len[i])].tolist()):
+                raise ValueError(f"pair {i}: a target id is not in its source (the reference's loss is inf there)")
+        encoder = isinstance(conditions, str)
+        if encoder:
+            if conditions != "encoder":
+                raise ValueError(f"conditions must be 'encoder' or a [n_w, n_pair, K] tensor, not {conditions!r}")
+            if not self.has_condition_encoder:
+                raise ValueError("conditions='encoder' needs condition_encoder.* and this state dict has none")
+            if noise is not None and tuple(torch.as_tensor(noise).shape) != (n, self.K):
+                raise ValueError(f"noise of shape {tuple(torch.as_tensor(noise).shape)}, expected ({n}, {self.K})")
+        else:
+            conditions = torch.as_tensor(conditions)
+            if conditions.dim() != 3 or tuple(conditions.shape[1:]) != (n, self.K):
+                raise ValueError(f"condition weights of shape {tuple(conditions.shape)}, expected [n_w, {n}, {self.K}]")
+        if backend == "hip":
+            return self._loss_and_grad_hip(src, src_len, tgt, tgt_len, T, conditions, causal_source, noise, tau, entropy_weight)
+        dev = self.device
+        n_tok = max(int((tgt[:, 1:] != 0).sum()), 1)
+        leaves = {k: v.to(device=dev, dtype=dtype).clone().requires_grad_(True) for k, v in self.p.items()}
+        loss = torch.zeros((), dtype=torch.float64)
+        entropy = torch.zeros((), dtype=torch.float64)
+        dws, conds = [], []
+        for a in range(0, n, ROWS_PER_TORCH):
+            b = min(n, a + ROWS_PER_TORCH)
+            s_d, t_d, tl_d = src[a:b].to(dev), tgt[a:b].to(dev), tgt_len[a:b].to(dev)
+            ent = None
+            if encoder:
+                _, c = self._score_torch(s_d, t_d, tl_d, None, True, causal_source, dtype, leaves)
+                z = c if noise is None else c + torch.as_tensor(noise)[a:b].to(dev, dtype)
+                w0 = torch.softmax(z / tau, -1)
+                ent = -(w0 * torch.log(w0 + 1e-12)).sum(-1).sum() / n
+                w = w0[None]                                          # its .grad is the cross entropy's alone: what the kernels call dw
+            else:
+                c = None
+                w = conditions[:, a:b].to(dev, dtype).clone().requires_grad_(True)
+            w.retain_grad()
+            nll, c2 = self._score_torch(s_d, t_d, tl_d, w, self.has_condition_encoder and c is None, causal_source, dtype, leaves)
+            ce = nll.sum() / n_tok
+            (ce if ent is None else ce + entropy_weight * ent).backward()
+            loss += float(ce.detach())
+            if ent is not None:
+                entropy += float(ent.detach())
+            dws.append(w.grad.detach())
+            c = c2 if c is None else c
+            if c is not None:
+                conds.append(c.detach())
+        grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
+        n_w = 1 if encoder else conditions.shape[0]
+        return GradResult(loss, entropy if encoder else None, grads,
+                          torch.cat(dws, 1) if dws else torch.zeros(n_w, 0, self.K, dtype=dtype, device=dev),
+                          torch.cat(conds) if conds else None)
+
     @torch.no_grad()
     def score(self, pairs, conditions="all", causal_source: bool = True, width=None, backend: str = "hip", dtype=torch.float32):
         """Teacher-forced per-token NLL of every (sequence, pattern) pair — the forward and loss of 2.Pretrain_regenerator.py's
@@ -546,6 +787,15 @@ class RegenModel:
         n_w = 1 if w is None else w.shape[0]
         nll = torch.cat(nll, 1) if nll else torch.zeros(n_w, 0, T, dtype=odt)
         return ScoreResult(nll, (tgt[:, 1:] != 0).sum(1), torch.cat(cond) if cond else None, Ls, T)
+
+
+class GradResult:
+    """RegenModel.loss_and_grad's result: loss (float64 scalar: the cross entropy summed over the weight vectors), entropy (float64
+    scalar, the mean condition entropy; None for constant weights), grads (state-dict name -> tensor), dw [n_w, n_pair, K] (the
+    gradient with respect to the condition weights) and cond_logits [n_pair, K] or None"""
+
+    def __init__(self, loss, entropy, grads, dw, cond_logits):
+        self.loss, self.entropy, self.grads, self.dw, self.cond_logits = loss, entropy, grads, dw, cond_logits
 
 
 class ScoreResult:

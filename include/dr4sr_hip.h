@@ -698,6 +698,31 @@ int dr4sr_regen_score(const dr4sr_regen_plan* plan, const int64_t* src, const in
                       int64_t n_pair, int32_t Ls, int32_t T, const float* w, int32_t n_w, int32_t causal_source, void* workspace,
                       int64_t workspace_bytes, float* nll, void* stream);
 
+/* Gradients of teacher-forced scoring (csrc/regen_score_bwd.hip), additive to ABI 10.  Common to both calls: self-contained (each runs
+ * the forward it needs), only enqueues on `stream` (capturable, no memset nodes), no floating-point atomics (the same call on the same
+ * inputs gives the same bits); `grad` is a flat buffer in the 98-tensor score layout, accumulate = 0 overwrites every element of it,
+ * accumulate = 1 adds; the workspace needs no initialisation.  Return codes and argument checks as dr4sr_regen_score. */
+
+/* The vector-Jacobian product of dr4sr_regen_score: dnll [n_w, n_pair, T] (ignored where the target is PAD or outside its source: such a
+ * token contributes nothing) -> grad (transformer.*, condition_linear.* and the two tables; the table takes its three terms: source
+ * lookups, target lookups and the restricted logits, PAD row 0 through the logits of a padded source row) and dw [n_w, n_pair, K], the
+ * gradient with respect to the condition weights.  nll_or_null, when given, receives the forward's NLLs [n_w, n_pair, T].  The workspace
+ * is large (about 20 KB per decoder token slot and 26 KB per source position: ~2 MB per pair at Ls = 50, n_w = 1): callers chunk, the
+ * Python wrapper at 256 pairs. */
+int64_t dr4sr_regen_score_bwd_workspace_bytes(const dr4sr_regen_plan* plan, int64_t n_pair, int32_t Ls, int32_t T, int32_t n_w);
+int dr4sr_regen_score_bwd(const dr4sr_regen_plan* plan, const int64_t* src, const int64_t* src_len, const int64_t* tgt, const int64_t* tgt_len,
+                          int64_t n_pair, int32_t Ls, int32_t T, const float* w, int32_t n_w, int32_t causal_source, const float* dnll,
+                          void* workspace, int64_t workspace_bytes, float* grad, float* dw, float* nll_or_null, int32_t accumulate,
+                          void* stream);
+
+/* The vector-Jacobian product of dr4sr_regen_score_condition: dlogits [n_pair, K] -> grad (condition_encoder.*, the item table and the
+ * position table receive values).  Workspace: about 16 KB per token slot, 64 slots per tile of 65 - T live tokens, sized for
+ * n_pair * T tokens. */
+int64_t dr4sr_regen_score_condition_bwd_workspace_bytes(const dr4sr_regen_plan* plan, int64_t n_pair, int32_t T);
+int dr4sr_regen_score_condition_bwd(const dr4sr_regen_plan* plan, const int64_t* tgt, const int64_t* tgt_len, int64_t n_pair, int32_t T,
+                                    const float* dlogits, void* workspace, int64_t workspace_bytes, float* grad, int32_t accumulate,
+                                    void* stream);
+
 /* Test / measurement hooks (dr4sr_dropout_mask, dr4sr_*_launch_kernel) are NOT part of this product surface: they are declared in
  * include/dr4sr_hip_hooks.h, and nothing under dr4sr_amd/ calls them. */
 
