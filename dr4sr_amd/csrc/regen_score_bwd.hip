@@ -12,8 +12,9 @@
 //                    encoder.norm and the two encoder layers (causal or bidirectional).
 //   k_rsb_cond_tile  the condition encoder (backward of k_rs_tile<0>): dlogits -> the two linears -> mean pooling (over len(t) + 2, as
 //                    the forward) -> 2 encoder layers -> the input rows.
-// Activations: every tile kernel recomputes its forward and writes what a weight gradient needs, and every per-token output gradient,
-// into the tile's slot RECORDS in the workspace (empty slots hold zero gradients and finite activations); the LDS holds one operation's
+// Activations: every tile kernel runs its forward again, through the same functions as the scoring kernels (regen_score_fwd.h) with
+// the KeepRec policy, which writes what a weight gradient needs into the tile's slot RECORDS in the workspace; the backward chain adds
+// every per-token output gradient (empty slots hold zero gradients and finite activations); the LDS holds one operation's
 // working set (the forward's layout + one score-gradient buffer).
 //   k_rsb_wgrad      every weight, bias and LayerNorm gradient as one job list: dW[n][k] = sum over records of dY[n] X[k] (a bias is the
 //                    job with X = 1).  The records are cut into NSPLIT contiguous ranges, each summed in record order into its own
@@ -23,7 +24,7 @@
 //                    records' rows (target lookups, source lookups, the logit term; positions likewise).
 // No floating-point atomics; every sum has a fixed order, so a call gives the same bits every time.  Kernels write their own zeros
 // (k_rsb_zero), nothing is memset.
-#include "regen_score_common.h"
+#include "regen_score_fwd.h"
 
 namespace {
 
@@ -42,9 +43,6 @@ struct WJob { int yoff, xoff, N, K, nkt, blk0, rep, ystep, xstep, pad; int64_t o
 struct WJobs { int n, nblk; WJob j[MAXJ]; };
 
 // `tf` is the record stride in floats, `rows` the number of records (rows of the tile) that exist
-__device__ __forceinline__ void save64(const float* L, int ld, float* rec, int field, int ncol, int tf = TOKF, int rows = TM) {
-    for (int e = threadIdx.x; e < rows * ncol; e += NT) rec[(size_t)(e / ncol) * tf + field + e % ncol] = L[(e / ncol) * ld + e % ncol];
-}
 __device__ __forceinline__ void load64(float* L, int ld, const float* rec, int field, int ncol, int tf = TOKF, int rows = TM) {
     for (int e = threadIdx.x; e < TM * ncol; e += NT)
         L[(e / ncol) * ld + e % ncol] = e / ncol < rows ? rec[(size_t)(e / ncol) * tf + field + e % ncol] : 0.f;
@@ -57,20 +55,6 @@ __device__ __forceinline__ void gemm_dx(const float* A, int lda, const float* __
     acc_zero(acc);
     mma_64xN_wT<KR, NTW>(A, lda, W, ldw, acc);
     acc_to_lds<NTW>(acc, Y, ldy, nullptr);
-}
-
-// add_ln64 that also stores the LayerNorm's input X + A in the slot records
-__device__ __forceinline__ void add_ln64_save(float* X, const float* A, int lda, const float* __restrict__ w, const float* __restrict__ b, float eps,
-                                              float* rec, int field, int tf = TOKF, int rows = TM) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int r = wv; r < TM; r += NT / 64) {
-        const float v = X[r * XLD + lane] + (A ? A[r * lda + lane] : 0.f);
-        if (r < rows) rec[(size_t)r * tf + field + lane] = v;
-        const float mean = wave_sum(v) * (1.0f / RD);
-        const float d = v - mean;
-        const float var = wave_sum(d * d) * (1.0f / RD);
-        X[r * XLD + lane] = d * rsqrtf(var + eps) * w[lane] + b[lane];
-    }
 }
 
 // LayerNorm backward of the 64 rows: X holds dL/dy and leaves dL/d(input); the records take dy * xhat, dy and the input gradient
@@ -186,98 +170,29 @@ __global__ __launch_bounds__(NT) void k_rsb_cond_tile(const float* __restrict__ 
     float* U = Tt + TM * XLD;                      // [64][FLD]
     float* PS = U + TM * FLD;                      // [64][RH][PLD] attention probabilities
     float* DS = PS + TM * RH * PLD;                // [64][RH][PLD] score gradients
-    const int64_t lo_g = (int64_t)blockIdx.x * S, hi_g = lo_g + S;
-    if (lo_g >= (int64_t)cum[n_pair]) return;
-    if (threadIdx.x < TM) tb.tok_row[threadIdx.x] = -1;
-    if (threadIdx.x == 0) {
-        int a = 0, b = n_pair;                     // the last pair that starts at or before lo_g
-        while (b - a > 1) {
-            const int mid = (a + b) >> 1;
-            if ((int64_t)cum[mid] <= lo_g) a = mid; else b = mid;
-        }
-        int nr = 0;
-        for (int p = a; p < n_pair; ++p) {
-            const int64_t st = cum[p];
-            if (st < lo_g) continue;
-            if (st >= hi_g) break;
-            tb.row_pair[nr] = p; tb.row_w[nr] = 0; tb.row_base[nr] = (int)(st - lo_g); tb.row_n[nr] = cum[p + 1] - cum[p];
-            ++nr;
-        }
-        tb.n_row = nr;
-    }
-    __syncthreads();
+    if (!build_tile_tab<0, false>(tb, n_rows, K, nullptr, 1, tgt, n_pair, T, nullptr, 1, cum, S)) return;
     const int n_row = tb.n_row;
-    if (threadIdx.x < n_row) {
-        const int r = threadIdx.x, p = tb.row_pair[r], base = tb.row_base[r], n = tb.row_n[r];
-        for (int t = 0; t < n; ++t) {
-            tb.tok_row[base + t] = r;
-            tb.tok_pos[base + t] = t;
-            tb.tok_id[base + t] = clampi(tgt[(int64_t)p * (T + 1) + t], 0, n_rows - 1);
-        }
-    }
-    __syncthreads();
     float* rec = slab + (size_t)blockIdx.x * TM * TOKF;
     if (threadIdx.x < TM) {
         const int s = threadIdx.x, live = tb.tok_row[s] >= 0;
         slot_id[(size_t)blockIdx.x * TM + s] = live ? tb.tok_id[s] : -1;
         slot_pos[(size_t)blockIdx.x * TM + s] = live ? tb.tok_pos[s] : -1;
     }
-    const float* E = P + off.o[T_E];
-    const float* Pos = P + off.o[T_P];
-    for (int e = threadIdx.x; e < TM * RD; e += NT) {
-        const int s = e / RD, c = e % RD;
-        X[s * XLD + c] = tb.tok_row[s] >= 0 ? E[(size_t)tb.tok_id[s] * RD + c] + Pos[tb.tok_pos[s] * RD + c] : 0.f;
-    }
+    embed_tile(P + off.o[T_E], P + off.o[T_P], X, tb);
     __syncthreads();
     const float scale = rsqrtf((float)RDH);
-    // ---- forward, as k_rs_tile<0>, keeping what the backward reads
+    // ---- the forward of k_rs_tile<0>, keeping what the backward reads (row r of the tile's pooling sits in record r)
+    const KeepRec keep{rec, TOKF, TM};
     for (int l = 0; l < RNL; ++l) {
         const int64_t* lo = off.o + T_CENC + 12 * l;
         const int f = l * LF;
-        save64(X, XLD, rec, f + F_X, RD);
-        gemm64<RD, 3, 0>(X, XLD, P + lo[E_INW], P + lo[E_INB], U, QLD);
-        __syncthreads();
-        save64(U, QLD, rec, f + F_QKV, 3 * RD);
-        self_attention(tb, U, PS, Tt, scale);
-        __syncthreads();
-        save64(Tt, XLD, rec, f + F_O, RD);
-        gemm64<RD, 1, 0>(Tt, XLD, P + lo[E_OUTW], P + lo[E_OUTB], U, XLD);
-        __syncthreads();
-        add_ln64_save(X, U, XLD, P + lo[E_N1W], P + lo[E_N1B], eps, rec, f + F_V1);
-        __syncthreads();
-        save64(X, XLD, rec, f + F_X1, RD);
-        gemm64<RD, 4, 0>(X, XLD, P + lo[E_W1], P + lo[E_B1], U, FLD);
-        __syncthreads();
-        for (int e = threadIdx.x; e < TM * RF; e += NT) {
-            const int s = e / RF, c = e % RF;
-            const float v = U[s * FLD + c];
-            const float g = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-            rec[(size_t)s * TOKF + f + F_HP + c] = v;
-            rec[(size_t)s * TOKF + f + F_HH + c] = g;
-            U[s * FLD + c] = g;
-        }
-        __syncthreads();
-        gemm64<RF, 1, 0>(U, FLD, P + lo[E_W2], P + lo[E_B2], Tt, XLD);
-        __syncthreads();
-        add_ln64_save(X, Tt, XLD, P + lo[E_N2W], P + lo[E_N2B], eps, rec, f + F_V2);
-        __syncthreads();
+        self_block_fwd(keep, {f + F_X, f + F_QKV, f + F_O, f + F_V1}, P, lo, E_INW, E_OUTW, E_N1W, eps, X, Tt, U,
+                       [&] { self_attention(tb, U, PS, Tt, scale); });
+        ffn_block_fwd(keep, {f + F_X1, f + F_HP, f + F_HH, f + F_V2}, P, lo, E_W1, E_W2, E_N2W, eps, X, Tt, U);
     }
-    // ---- mean pooling and condition_layer[0] + ReLU (row r of the tile sits in record r)
-    for (int e = threadIdx.x; e < TM * RD; e += NT) {
-        const int r = e / RD, c = e % RD;
-        float a = 0.f;
-        if (r < n_row) {
-            const int base = tb.row_base[r], n = tb.row_n[r];
-            for (int t = 0; t < n; ++t) a += X[(base + t) * XLD + c];
-            a = a / (float)max<int64_t>(tgt_len[tb.row_pair[r]], 1);
-        }
-        Tt[r * XLD + c] = a;
-    }
-    __syncthreads();
-    gemm64<RD, 1, 1>(Tt, XLD, P + off.o[T_CC0W], P + off.o[T_CC0B], U, XLD);
-    __syncthreads();
-    save64(Tt, XLD, rec, F_POOL, RD);
-    save64(U, XLD, rec, F_HID, RD);
+    pool_and_hidden(tb, n_row, tgt_len, P, off, X, Tt, U);
+    keep.save(Tt, XLD, F_POOL, RD);
+    keep.save(U, XLD, F_HID, RD);
     // ---- backward of the two linears and of the pooling
     const float* W2c = P + off.o[T_CC2W];
     for (int e = threadIdx.x; e < TM * RD; e += NT) {
@@ -351,88 +266,6 @@ enum { R_X = 0, R_QKV = 64, R_O = 256, R_V1 = 320, R_X1 = 384, R_QC = 448, R_OC 
 constexpr int R_VN = RNL * LFD, R_GN = R_VN + 64, R_YN = R_GN + 64, R_DX0 = R_YN + 64, TOKD = R_DX0 + 64;
 static_assert(R_Y3 + 64 == LFD && TOKD % 4 == 0, "decoder slot record layout");
 constexpr int KVW = RNL * 2 * RD;      // floats per (row, source position) of the mixed-memory gradient: [layer][K | V]
-
-__device__ __forceinline__ bool src_live(const int64_t* __restrict__ src, int64_t p, int Ls, int j, int n_rows) {
-    return clampi(src[p * Ls + j], 0, n_rows - 1) != 0;
-}
-
-// head h's 32 features at column `col` (0: K, RD: V) of the row's mixed memory at source position j, bias included
-__device__ __forceinline__ void mix_kv(const TileTab& tb, int r, int K, int Ls, int l, int j, int col, const float* __restrict__ ckv,
-                                       const float* __restrict__ cb, float (&kv)[RDH]) {
-    const int64_t p = tb.row_pair[r];
-#pragma unroll
-    for (int d = 0; d < RDH; ++d) kv[d] = 0.f;
-    for (int k = 0; k < K; ++k) {
-        const float wk = tb.row_wt[r][k];
-        const float* c = ckv + (((p * K + k) * RNL + l) * Ls + j) * (2 * RD) + col;
-#pragma unroll
-        for (int d = 0; d < RDH; d += 4) {
-            const float4 v = ld4(c + d);
-            kv[d] = fmaf(wk, v.x, kv[d]); kv[d + 1] = fmaf(wk, v.y, kv[d + 1]);
-            kv[d + 2] = fmaf(wk, v.z, kv[d + 2]); kv[d + 3] = fmaf(wk, v.w, kv[d + 3]);
-        }
-    }
-#pragma unroll
-    for (int d = 0; d < RDH; ++d) kv[d] += cb[RD + col + d];
-}
-
-// cross-attention probabilities of every live slot over its row's source positions, as k_rs_tile<1> computes them; Q [64][XLD]
-__device__ __forceinline__ void cross_probs(const TileTab& tb, int n_row, int K, int Ls, int n_rows, int l, const int64_t* __restrict__ src,
-                                            const float* __restrict__ ckv, const float* __restrict__ cb, const float* Q, float* PS, float scale) {
-    for (int e = threadIdx.x; e < n_row * RH * LMAX; e += NT) {
-        const int r = e / (RH * LMAX), h = (e / LMAX) % RH, j = e % LMAX;
-        const int base = tb.row_base[r], n = tb.row_n[r];
-        if (j >= tb.row_ls[r]) continue;
-        const bool live = src_live(src, tb.row_pair[r], Ls, j, n_rows);
-        float kv[RDH];
-        if (live) mix_kv(tb, r, K, Ls, l, j, h * RDH, ckv, cb, kv);
-        for (int t = 0; t < n; ++t) {
-            float v = -INFINITY;
-            if (live) {
-                const float* q = Q + (base + t) * XLD + h * RDH;
-                float a = 0.f;
-#pragma unroll
-                for (int d = 0; d < RDH; ++d) a = fmaf(q[d], kv[d], a);
-                v = a * scale;
-            }
-            PS[((base + t) * RH + h) * PLD + j] = v;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < TM * RH) {
-        const int r = tb.tok_row[threadIdx.x >> 1];
-        if (r >= 0) softmax_masked(PS + threadIdx.x * PLD, tb.row_ls[r]);
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ void cross_out(const TileTab& tb, int n_row, int K, int Ls, int l, const float* __restrict__ ckv,
-                                          const float* __restrict__ cb, const float* PS, float* O) {
-    for (int e = threadIdx.x; e < TM * RD; e += NT)
-        if (tb.tok_row[e / RD] < 0) O[(e / RD) * XLD + e % RD] = 0.f;
-    for (int e = threadIdx.x; e < n_row * RD; e += NT) {
-        const int r = e / RD, c = e % RD, h = c / RDH;
-        const int64_t p = tb.row_pair[r];
-        const int base = tb.row_base[r], n = tb.row_n[r], ls = tb.row_ls[r];
-        const float bv = cb[2 * RD + c];
-        for (int t0 = 0; t0 < n; t0 += 8) {
-            float acc[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc[u] = 0.f;
-            for (int j = 0; j < ls; ++j) {
-                float v = 0.f;
-                for (int k = 0; k < K; ++k) v = fmaf(tb.row_wt[r][k], ckv[(((p * K + k) * RNL + l) * Ls + j) * (2 * RD) + RD + c], v);
-                v += bv;
-#pragma unroll
-                for (int u = 0; u < 8; ++u)
-                    if (t0 + u < n) acc[u] = fmaf(PS[((base + t0 + u) * RH + h) * PLD + j], v, acc[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (t0 + u < n) O[(base + t0 + u) * XLD + c] = acc[u];
-        }
-    }
-}
 
 // backward of the cross-attention: Q and dO [64][XLD] in LDS, PS holds the probabilities -> dQ [64][XLD] in LDS and the gradient of
 // the row's mixed K | V into dkv[row][j][layer][K | V] (zero where the key is masked or beyond the source)
@@ -535,44 +368,8 @@ __global__ __launch_bounds__(NT) void k_rsb_dec_tile(const float* __restrict__ P
     float* U = Tt + TM * XLD;                      // [64][FLD]; in the cross-attention backward: q [64][XLD] then dq [64][XLD]
     float* PS = U + TM * FLD;
     float* DS = PS + TM * RH * PLD;
-    const int64_t lo_g = (int64_t)blockIdx.x * S, hi_g = lo_g + S;
-    if (lo_g >= (int64_t)n_w * cum[n_pair]) return;
-    if (threadIdx.x < TM) tb.tok_row[threadIdx.x] = -1;
-    if (threadIdx.x == 0) {
-        int a = 0, b = n_pair;
-        while (b - a > 1) {
-            const int mid = (a + b) >> 1;
-            if ((int64_t)n_w * cum[mid] <= lo_g) a = mid; else b = mid;
-        }
-        int nr = 0;
-        for (int p = a; p < n_pair; ++p) {
-            const int64_t base = (int64_t)n_w * cum[p];
-            if (base >= hi_g) break;
-            const int np = cum[p + 1] - cum[p];
-            for (int i = 0; i < n_w; ++i) {
-                const int64_t st = base + (int64_t)i * np;
-                if (st < lo_g) continue;
-                if (st >= hi_g) break;
-                tb.row_pair[nr] = p; tb.row_w[nr] = i; tb.row_base[nr] = (int)(st - lo_g); tb.row_n[nr] = np;
-                ++nr;
-            }
-        }
-        tb.n_row = nr;
-    }
-    __syncthreads();
+    if (!build_tile_tab<1, true>(tb, n_rows, K, src_len, Ls, tgt, n_pair, T, wts, n_w, cum, S)) return;
     const int n_row = tb.n_row;
-    if (threadIdx.x < n_row) {
-        const int r = threadIdx.x, p = tb.row_pair[r], base = tb.row_base[r], n = tb.row_n[r];
-        tb.row_ls[r] = clampi(src_len[p], 1, Ls);
-        for (int k = 0; k < K; ++k) tb.row_wt[r][k] = wts[((int64_t)tb.row_w[r] * n_pair + p) * K + k];
-        for (int t = 0; t < n; ++t) {
-            tb.tok_row[base + t] = r;
-            tb.tok_pos[base + t] = t;
-            tb.tok_id[base + t] = clampi(tgt[(int64_t)p * (T + 1) + t], 0, n_rows - 1);
-            tb.tok_out[base + t] = clampi(tgt[(int64_t)p * (T + 1) + t + 1], 0, n_rows - 1);
-        }
-    }
-    __syncthreads();
     float* rec = slab + (size_t)blockIdx.x * TM * TOKD;
     if (threadIdx.x < TM) {
         const int s = threadIdx.x, live = tb.tok_row[s] >= 0;
@@ -580,59 +377,20 @@ __global__ __launch_bounds__(NT) void k_rsb_dec_tile(const float* __restrict__ P
         slot_pos[(size_t)blockIdx.x * TM + s] = live ? tb.tok_pos[s] : -1;
     }
     const float* E = P + off.o[T_E];
-    const float* Pos = P + off.o[T_P];
-    for (int e = threadIdx.x; e < TM * RD; e += NT) {
-        const int s = e / RD, c = e % RD;
-        X[s * XLD + c] = tb.tok_row[s] >= 0 ? E[(size_t)tb.tok_id[s] * RD + c] + Pos[tb.tok_pos[s] * RD + c] : 0.f;
-    }
+    embed_tile(E, P + off.o[T_P], X, tb);
     __syncthreads();
     const float scale = rsqrtf((float)RDH);
-    // ---- forward, as k_rs_tile<1>, keeping what the backward reads
+    // ---- the forward of k_rs_tile<1>, keeping what the backward reads
+    const KeepRec keep{rec, TOKD, TM};
     for (int l = 0; l < RNL; ++l) {
         const int64_t* lo = off.o + T_DEC + 18 * l;
         const int f = l * LFD;
-        save64(X, XLD, rec, f + R_X, RD, TOKD);
-        gemm64<RD, 3, 0>(X, XLD, P + lo[D_SAINW], P + lo[D_SAINB], U, QLD);
-        __syncthreads();
-        save64(U, QLD, rec, f + R_QKV, 3 * RD, TOKD);
-        self_attention(tb, U, PS, Tt, scale);
-        __syncthreads();
-        save64(Tt, XLD, rec, f + R_O, RD, TOKD);
-        gemm64<RD, 1, 0>(Tt, XLD, P + lo[D_SAOUTW], P + lo[D_SAOUTB], U, XLD);
-        __syncthreads();
-        add_ln64_save(X, U, XLD, P + lo[D_N1W], P + lo[D_N1B], eps, rec, f + R_V1, TOKD);
-        __syncthreads();
-        save64(X, XLD, rec, f + R_X1, RD, TOKD);
-        gemm64<RD, 1, 0>(X, XLD, P + lo[D_CAINW], P + lo[D_CAINB], U, XLD);
-        __syncthreads();
-        save64(U, XLD, rec, f + R_QC, RD, TOKD);
-        const float* cb = P + lo[D_CAINB];
-        cross_probs(tb, n_row, K, Ls, n_rows, l, src, ckv, cb, U, PS, scale);
-        cross_out(tb, n_row, K, Ls, l, ckv, cb, PS, Tt);
-        __syncthreads();
-        save64(Tt, XLD, rec, f + R_OC, RD, TOKD);
-        gemm64<RD, 1, 0>(Tt, XLD, P + lo[D_CAOUTW], P + lo[D_CAOUTB], U, XLD);
-        __syncthreads();
-        add_ln64_save(X, U, XLD, P + lo[D_N2W], P + lo[D_N2B], eps, rec, f + R_V2, TOKD);
-        __syncthreads();
-        save64(X, XLD, rec, f + R_X2, RD, TOKD);
-        gemm64<RD, 4, 0>(X, XLD, P + lo[D_W1], P + lo[D_B1], U, FLD);
-        __syncthreads();
-        for (int e = threadIdx.x; e < TM * RF; e += NT) {
-            const int s = e / RF, c = e % RF;
-            const float v = U[s * FLD + c];
-            const float g = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-            rec[(size_t)s * TOKD + f + R_HP + c] = v;
-            rec[(size_t)s * TOKD + f + R_HH + c] = g;
-            U[s * FLD + c] = g;
-        }
-        __syncthreads();
-        gemm64<RF, 1, 0>(U, FLD, P + lo[D_W2], P + lo[D_B2], Tt, XLD);
-        __syncthreads();
-        add_ln64_save(X, Tt, XLD, P + lo[D_N3W], P + lo[D_N3B], eps, rec, f + R_V3, TOKD);
-        __syncthreads();
+        self_block_fwd(keep, {f + R_X, f + R_QKV, f + R_O, f + R_V1}, P, lo, D_SAINW, D_SAOUTW, D_N1W, eps, X, Tt, U,
+                       [&] { self_attention(tb, U, PS, Tt, scale); });
+        cross_block_fwd(keep, {f + R_X1, f + R_QC, f + R_OC, f + R_V2}, tb, n_row, K, Ls, n_rows, l, src, ckv, P, lo, eps, X, Tt, U, PS, scale);
+        ffn_block_fwd(keep, {f + R_X2, f + R_HP, f + R_HH, f + R_V3}, P, lo, D_W1, D_W2, D_N3W, eps, X, Tt, U);
     }
-    save64(X, XLD, rec, R_VN, RD, TOKD);
+    keep.save(X, XLD, R_VN, RD);
     __syncthreads();
     add_ln64(X, nullptr, 0, P + off.o[T_DEC_NORM], P + off.o[T_DEC_NORM + 1], eps);
     __syncthreads();
@@ -643,32 +401,11 @@ __global__ __launch_bounds__(NT) void k_rsb_dec_tile(const float* __restrict__ P
         const int r = tb.tok_row[s];
         if (r < 0) { DL[s * RH * PLD + lane] = 0.f; continue; }
         const int p = tb.row_pair[r], want = tb.tok_out[s];
-        const int id = lane < Ls ? clampi(src[(int64_t)p * Ls + lane], 0, n_rows - 1) : -1;
-        bool first = lane < Ls;
-        for (int j = 0; j < Ls; ++j) {
-            const int other = __shfl(id, j, 64);
-            if (j < lane && other == id) first = false;
-        }
-        float a = 0.f;
-        if (first) {
-            const float* e = E + (size_t)id * RD;
-            for (int c = 0; c < RD; c += 4) {
-                const float4 ev = ld4(e + c);
-                a = fmaf(X[s * XLD + c], ev.x, a); a = fmaf(X[s * XLD + c + 1], ev.y, a);
-                a = fmaf(X[s * XLD + c + 2], ev.z, a); a = fmaf(X[s * XLD + c + 3], ev.w, a);
-            }
-        }
-        float m = first ? a : -INFINITY;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        const float ex = first ? expf(a - m) : 0.f;
-        const float sum = wave_sum(ex);
-        const bool hit = first && id == want;
-        const bool any = __ballot(hit) != 0ull;
+        const RLogit o = restricted_logit(E, src, p, Ls, n_rows, X + s * XLD, want);
         const int64_t ri = (int64_t)tb.row_w[r] * n_pair + p;
-        const float g = (want != 0 && any) ? dnll[ri * T + tb.tok_pos[s]] : 0.f;     // a target outside its source contributes nothing
-        DL[s * RH * PLD + lane] = first ? g * (ex / sum - (hit ? 1.f : 0.f)) : 0.f;
-        if (tb.tok_pos[s] == 0 && lane < Ls) lkey[ri * Ls + lane] = first ? id : -1;
+        const float g = (want != 0 && o.any) ? dnll[ri * T + tb.tok_pos[s]] : 0.f;   // a target outside its source contributes nothing
+        DL[s * RH * PLD + lane] = o.first ? g * (o.ex / o.sum - (o.hit ? 1.f : 0.f)) : 0.f;
+        if (tb.tok_pos[s] == 0 && lane < Ls) lkey[ri * Ls + lane] = o.first ? o.id : -1;
     }
     __syncthreads();
     for (int e = threadIdx.x; e < TM * RD; e += NT) {                                // d(decoder.norm output)
@@ -725,7 +462,7 @@ __global__ __launch_bounds__(NT) void k_rsb_dec_tile(const float* __restrict__ P
         float* DQ = U + TM * XLD;
         cross_bwd(tb, n_row, K, Ls, n_rows, n_pair, l, src, ckv, cb, U, Tt, PS, DS, DQ, dkv, scale);
         __syncthreads();
-        save64(DQ, XLD, rec, f + R_DQC, RD, TOKD);
+        keep.save(DQ, XLD, f + R_DQC, RD);
         gemm_dx<RD, 1>(DQ, XLD, P + lo[D_CAINW], Tt, XLD);
         __syncthreads();
         add64(X, Tt);
@@ -779,25 +516,6 @@ constexpr int S_VN = RNL * LF, S_GN = S_VN + 64, S_YN = S_GN + 64, S_MEMN = S_YN
 static_assert(TOKS % 4 == 0, "source record layout");
 constexpr int ALD = 2 * RD + 4;
 
-// the source encoder's attention probabilities S[h][i][j], as k_rs_source computes them
-__device__ __forceinline__ void src_probs(const float* QKV, float* S, const int* ids, int n, int causal, float scale) {
-    for (int e = threadIdx.x; e < RH * n * LMAX; e += NT) {
-        const int h = e / (n * LMAX), i = (e / LMAX) % n, j = e % LMAX;
-        float v = -INFINITY;
-        if (j < n && ids[j] != 0 && (!causal || j <= i)) {
-            const float* q = QKV + i * QLD + h * RDH;
-            const float* k = QKV + j * QLD + RD + h * RDH;
-            float a = 0.f;
-            for (int d = 0; d < RDH; ++d) a = fmaf(q[d], k[d], a);
-            v = a * scale;
-        }
-        S[(h * LMAX + i) * LMAX + j] = v;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < RH * n; e += NT) softmax_masked(S + ((e / n) * LMAX + e % n) * LMAX, n);
-    __syncthreads();
-}
-
 template <int KC>
 __global__ __launch_bounds__(NT) void k_rsb_source(const float* __restrict__ P, ScoreOff off, float eps, int n_rows,
                                                    const int64_t* __restrict__ src, const int64_t* __restrict__ src_len, int Ls, int causal,
@@ -813,78 +531,28 @@ __global__ __launch_bounds__(NT) void k_rsb_source(const float* __restrict__ P, 
     const int64_t p = blockIdx.x;
     const int n = clampi(src_len[p], 1, Ls);
     float* rec = slab + (size_t)p * Ls * TOKS;
-    const float* E = P + off.o[T_E];
-    const float* Pos = P + off.o[T_P];
     if (threadIdx.x < TM) ids[threadIdx.x] = threadIdx.x < n ? clampi(src[p * Ls + threadIdx.x], 0, n_rows - 1) : 0;
     __syncthreads();
     if (threadIdx.x < Ls) {
         key_id[p * Ls + threadIdx.x] = threadIdx.x < n ? ids[threadIdx.x] : -1;
         key_pos[p * Ls + threadIdx.x] = threadIdx.x < n ? (int)threadIdx.x : -1;
     }
-    for (int e = threadIdx.x; e < TM * RD; e += NT) {
-        const int j = e / RD, c = e % RD;
-        X[j * XLD + c] = j < n ? E[(size_t)ids[j] * RD + c] + Pos[j * RD + c] : 0.f;
-    }
+    embed_rows(P + off.o[T_E], P + off.o[T_P], X, [&](int j, int& id, int& pos) { id = ids[j]; pos = j; return j < n; });
     __syncthreads();
     const float scale = rsqrtf((float)RDH);
     float* QKV = U;                                // [64][QLD]
     float* S = U + TM * QLD;                       // [RH][LMAX][LMAX]
     float* DSb = S + RH * LMAX * LMAX;             // [RH][LMAX][LMAX]
-    // ---- forward, as k_rs_source, keeping what the backward reads
+    // ---- the forward of k_rs_source, keeping what the backward reads: only the Ls records of the pair exist
+    const KeepRec keep{rec, TOKS, Ls};
     for (int l = 0; l < RNL; ++l) {
         const int64_t* lo = off.o + T_ENC + 12 * l;
         const int f = l * LF;
-        save64(X, XLD, rec, f + F_X, RD, TOKS, Ls);
-        gemm64<RD, 3, 0>(X, XLD, P + lo[E_INW], P + lo[E_INB], QKV, QLD);
-        __syncthreads();
-        save64(QKV, QLD, rec, f + F_QKV, 3 * RD, TOKS, Ls);
-        src_probs(QKV, S, ids, n, causal, scale);
-        for (int e = threadIdx.x; e < TM * RD; e += NT) {
-            const int i = e / RD, c = e % RD, h = c / RDH;
-            float a = 0.f;
-            if (i < n) {
-                const float* pr = S + (h * LMAX + i) * LMAX;
-                for (int j = 0; j < n; ++j) a = fmaf(pr[j], QKV[j * QLD + 2 * RD + c], a);
-            }
-            T[i * XLD + c] = a;
-        }
-        __syncthreads();
-        save64(T, XLD, rec, f + F_O, RD, TOKS, Ls);
-        gemm64<RD, 1, 0>(T, XLD, P + lo[E_OUTW], P + lo[E_OUTB], U, XLD);
-        __syncthreads();
-        add_ln64_save(X, U, XLD, P + lo[E_N1W], P + lo[E_N1B], eps, rec, f + F_V1, TOKS, Ls);
-        __syncthreads();
-        save64(X, XLD, rec, f + F_X1, RD, TOKS, Ls);
-        gemm64<RD, 4, 0>(X, XLD, P + lo[E_W1], P + lo[E_B1], U, FLD);
-        __syncthreads();
-        for (int e = threadIdx.x; e < TM * RF; e += NT) {
-            const int s = e / RF, c = e % RF;
-            const float v = U[s * FLD + c];
-            const float g = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-            if (s < Ls) {
-                rec[(size_t)s * TOKS + f + F_HP + c] = v;
-                rec[(size_t)s * TOKS + f + F_HH + c] = g;
-            }
-            U[s * FLD + c] = g;
-        }
-        __syncthreads();
-        gemm64<RF, 1, 0>(U, FLD, P + lo[E_W2], P + lo[E_B2], T, XLD);
-        __syncthreads();
-        add_ln64_save(X, T, XLD, P + lo[E_N2W], P + lo[E_N2B], eps, rec, f + F_V2, TOKS, Ls);
-        __syncthreads();
+        self_block_fwd(keep, {f + F_X, f + F_QKV, f + F_O, f + F_V1}, P, lo, E_INW, E_OUTW, E_N1W, eps, X, T, U,
+                       [&] { src_probs(QKV, S, ids, n, causal, scale); src_context(QKV, S, n, T); });
+        ffn_block_fwd(keep, {f + F_X1, f + F_HP, f + F_HH, f + F_V2}, P, lo, E_W1, E_W2, E_N2W, eps, X, T, U);
     }
-    add_ln64_save(X, nullptr, 0, P + off.o[T_ENC_NORM], P + off.o[T_ENC_NORM + 1], eps, rec, S_VN, TOKS, Ls);
-    __syncthreads();
-    save64(X, XLD, rec, S_MEMN, RD, TOKS, Ls);
-    gemm64<RD, KC, 1>(X, XLD, P + off.o[T_CL0W], P + off.o[T_CL0B], U, CLD);
-    __syncthreads();
-    save64(U, CLD, rec, S_C1, KD, TOKS, Ls);
-    for (int k = 0; k < KC; ++k) {
-        gemm64<KD, 1, 0>(U, CLD, P + off.o[T_CL2W] + (size_t)k * RD * KD, P + off.o[T_CL2B] + k * RD, T, XLD);
-        __syncthreads();
-        save64(T, XLD, rec, S_MEM + k * RD, RD, TOKS, Ls);
-        __syncthreads();
-    }
+    source_tail_fwd<KC>(keep, {S_VN, S_MEMN, S_C1}, P, off, eps, X, T, U, [&](int k) { keep.save(T, XLD, S_MEM + k * RD, RD); });
     // ---- backward.  d(K | V)_k of condition k = sum over the pair's weight vectors of w_k d(K | V), in vector order
     float* DM = U;                                 // [64][CLD]: d(memory), condition k at columns 64 k
     float* A = U + TM * CLD;                       // [64][ALD]
@@ -910,7 +578,7 @@ __global__ __launch_bounds__(NT) void k_rsb_source(const float* __restrict__ P, 
             __syncthreads();
         }
     }
-    save64(DM, CLD, rec, S_DMEM, KD, TOKS, Ls);
+    keep.save(DM, CLD, S_DMEM, KD);
     for (int cbk = 0; cbk < KC; ++cbk) {               // d(condition_linear[0]'s output), 64 columns at a time
         gemm_dx<KD, 1>(DM, CLD, P + off.o[T_CL2W] + cbk * RD, T, XLD, KD);
         __syncthreads();
@@ -991,7 +659,7 @@ __global__ __launch_bounds__(NT) void k_rsb_source(const float* __restrict__ P, 
         add64(X, T);
         __syncthreads();
     }
-    save64(X, XLD, rec, S_DX0, RD, TOKS, Ls);
+    keep.save(X, XLD, S_DX0, RD);
 }
 template <int KC> constexpr size_t bwd_source_lds() {
     constexpr int CLD = KC * RD + 4;
@@ -1260,15 +928,9 @@ extern "C" int dr4sr_regen_score_bwd(const dr4sr_regen_plan* plan, const int64_t
     hipLaunchKernelGGL(k_rsb_dw, dim3((unsigned)((n_pair * n_w + 3) / 4)), dim3(256), 0, s, (const float*)dkv, (const float*)ckv, K, (int)n_pair,
                        n_w, Ls, dw);
     if (const int rc = DR4SR_LAUNCH_CHECK()) return rc;
-    int rc = 0;
-    const int causal = causal_source != 0;
-    switch (K) {
-        case 1: rc = launch_bwd_source<1>(plan, off, src, src_len, n_pair, Ls, causal, w, n_w, dkv, slab_s, sid, spos, s); break;
-        case 2: rc = launch_bwd_source<2>(plan, off, src, src_len, n_pair, Ls, causal, w, n_w, dkv, slab_s, sid, spos, s); break;
-        case 3: rc = launch_bwd_source<3>(plan, off, src, src_len, n_pair, Ls, causal, w, n_w, dkv, slab_s, sid, spos, s); break;
-        case 4: rc = launch_bwd_source<4>(plan, off, src, src_len, n_pair, Ls, causal, w, n_w, dkv, slab_s, sid, spos, s); break;
-        default: rc = launch_bwd_source<5>(plan, off, src, src_len, n_pair, Ls, causal, w, n_w, dkv, slab_s, sid, spos, s); break;
-    }
+    int rc = with_kc(K, [&](auto kc) {
+        return launch_bwd_source<decltype(kc)::value>(plan, off, src, src_len, n_pair, Ls, causal_source != 0, w, n_w, dkv, slab_s, sid, spos, s);
+    });
     if (rc) return rc;
     const int64_t pb = off.o[T_ENC];
     WJobs jd;                                       // the decoder's slot records

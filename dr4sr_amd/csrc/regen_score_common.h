@@ -1,5 +1,6 @@
-// regen_score_common.h — what the forward (regen_score.hip) and the backward (regen_score_bwd.hip) of teacher-forced scoring share:
-// the layout, the 64-row tile helpers, the live-token scan, the tile table with its causal self-attention, and the argument checks.
+// regen_score_common.h — the ground under teacher-forced scoring (regen_score.hip) and its gradients (regen_score_bwd.hip): the
+// parameter layout, the masked softmax, the live-token scan, the tile table with its causal self-attention, and the argument checks.
+// The forward that both files run is regen_score_fwd.h.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -32,41 +33,6 @@ int64_t score_layout(int32_t n_rows, int32_t K, int64_t* off) {
     const int64_t tail[4] = {RD * RD, RD, (int64_t)K * RD, (int64_t)K};
     for (int j = 0; j < 4; ++j) { if (off) off[i] = pos; ++i; pos += tail[j]; }
     return pos;
-}
-
-// Y[64][ldy] = act(A[64][K] W^T + bias) on the 32x32x2 MFMA tiles of common.h (W global [64 NTW][K]); Y must not alias A
-template <int K, int NTW, int ACT>     // ACT: 0 none, 1 ReLU, 2 erf-GELU
-__device__ __forceinline__ void gemm64(const float* A, int lda, const float* __restrict__ W, const float* __restrict__ bias, float* Y, int ldy) {
-    f32x16 acc[NTW];
-    acc_zero(acc);
-    mma_64xN<K, NTW>(A, lda, W, acc);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, g = lane >> 5, rh = w & 1, cg = w >> 1;
-#pragma unroll
-    for (int i = 0; i < NTW; ++i) {
-        const int col = (cg + 2 * i) * 32 + r;
-        const float bv = bias ? bias[col] : 0.f;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int row = rh * 32 + (q & 3) + 8 * (q >> 2) + 4 * g;
-            float v = acc[i][q] + bv;
-            if (ACT == 1) v = fmaxf(v, 0.f);
-            if (ACT == 2) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-            Y[row * ldy + col] = v;
-        }
-    }
-}
-
-// X[r] = LayerNorm(X[r] + A[r]) (A may be null) for the 64 rows; one wave per row, lane = feature
-__device__ __forceinline__ void add_ln64(float* X, const float* A, int lda, const float* __restrict__ w, const float* __restrict__ b, float eps) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int r = wv; r < TM; r += NT / 64) {
-        float v = X[r * XLD + lane];
-        if (A) v += A[r * lda + lane];
-        const float mean = wave_sum(v) * (1.0f / RD);
-        const float d = v - mean;
-        const float var = wave_sum(d * d) * (1.0f / RD);
-        X[r * XLD + lane] = d * rsqrtf(var + eps) * w[lane] + b[lane];
-    }
 }
 
 // softmax over j < n of S[j] in place; masked entries are -inf; a row with no live entry becomes all zero
