@@ -22,6 +22,10 @@
 //   k_rsb_reduce     grad += the NSPLIT partial slabs, added in slab order.
 //   k_rsb_embed      store-then-sum per destination: one workgroup per table row scans the record keys in order and adds the matching
 //                    records' rows (target lookups, source lookups, the logit term; positions likewise).
+// Train mode (the *_train entry points, DropPhilox policy): the forward drops at the reference's sites, so the records hold the post-dropout
+// GEMM inputs; the chain multiplies the gradient by the same regenerated factor at each site (drop_grad64 behind an output site, inside
+// the GELU loop for the hidden layer, on the input rows' gradient before the table sums); an attention block forms dP = (dO V^T) keep,
+// applies the softmax Jacobian to the UNDROPPED probabilities, and takes dV from the dropped ones.
 // No floating-point atomics; every sum has a fixed order, so a call gives the same bits every time.  Kernels write their own zeros
 // (k_rsb_zero), nothing is memset.
 #include "regen_score_fwd.h"
@@ -87,11 +91,60 @@ __device__ __forceinline__ float gelu_grad_exact(float x) {
     return fmaf(x * 0.39894228040143267794f, expf(-0.5f * x * x), cdf);
 }
 
+// the gradient behind an output dropout site: Y[64][XLD] = X keep on the live rows (the others are copied), and the record field that
+// held X (the linear's dY of the weight-gradient jobs) takes Y
+template <class Rows>
+__device__ __forceinline__ void drop_grad64(const DropPhilox& dp, uint32_t site, const Rows& rows, const float* X, float* Y, float* rec, int tf,
+                                            int field, int nrec) {
+    for (int u = threadIdx.x; u < TM * (RD / 8); u += NT) {
+        const int s = u / (RD / 8), c0 = (u % (RD / 8)) * 8;
+        const float4* x = reinterpret_cast<const float4*>(X + s * XLD + c0);
+        float4 a = x[0], b = x[1];
+        int64_t pair = 0;
+        int pos = 0;
+        if (rows(s, pair, pos)) {
+            float4 lo, hi;
+            drop8(dp.k, site, (uint64_t)((pair * 64 + pos) * RD + c0), lo, hi);
+            mul8(a, b, lo, hi);
+            if (s < nrec) {
+                float* rr = rec + (size_t)s * tf + field + c0;
+                st4(rr, a); st4(rr + 4, b);
+            }
+        }
+        float4* y = reinterpret_cast<float4*>(Y + s * XLD + c0);
+        y[0] = a; y[1] = b;
+    }
+}
+
+// U[64][FLD] = U keep gelu'(hp) over the first `nrec` rows, into the record's dhp too: the gradient behind the FFN's hidden site
+template <class Rows>
+__device__ __forceinline__ void gelu_bwd64(const DropPhilox& dp, uint32_t site, const Rows& rows, float* U, float* rec, int tf, int f_hp, int f_dhp,
+                                           int nrec) {
+    {
+        for (int u = threadIdx.x; u < nrec * (RF / 8); u += NT) {
+            const int s = u / (RF / 8), c0 = (u % (RF / 8)) * 8;
+            int64_t pair = 0;
+            int pos = 0;
+            float4 lo = make_float4(1.f, 1.f, 1.f, 1.f), hi = lo;
+            if (rows(s, pair, pos)) drop8(dp.k, site, (uint64_t)((pair * 64 + pos) * RF + c0), lo, hi);
+            const float m[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float d = U[s * FLD + c0 + i] * m[i] * gelu_grad_exact(rec[(size_t)s * tf + f_hp + c0 + i]);
+                U[s * FLD + c0 + i] = d;
+                rec[(size_t)s * tf + f_dhp + c0 + i] = d;
+            }
+        }
+    }
+}
+
 // backward of self_attention: QKV [64][QLD] and dO [64][XLD] in LDS -> dQKV into the slot records (gout = record base + field).
 // Pass A, a thread per (query slot, head): the probabilities again (PS), dS = p (dP - sum p dP) scale (DS), dQ.
 // Pass B, a thread per (key slot, head): dK and dV over the row's later queries, in query order.
-__device__ __forceinline__ void self_attention_bwd(const TileTab& tb, const float* QKV, const float* dO, float* PS, float* DS, float* gout,
-                                                   float scale, int tf = TOKF) {
+// Train mode: dP = (dO . V) keep, the Jacobian on the undropped p; pass A then leaves the DROPPED probabilities in PS for pass B's dV.
+template <class Drop>
+__device__ __forceinline__ void self_attention_bwd(const Drop& dp, uint32_t site, const TileTab& tb, const float* QKV, const float* dO, float* PS,
+                                                   float* DS, float* gout, float scale, int tf = TOKF) {
     const int s = threadIdx.x >> 1, h = threadIdx.x & 1;
     if (threadIdx.x < TM * RH) {
         const int r = tb.tok_row[s];
@@ -115,17 +168,21 @@ __device__ __forceinline__ void self_attention_bwd(const TileTab& tb, const floa
                 pr[j] = v;
             }
             softmax_masked(pr, nk);
+            uint64_t km = 0;
+            if constexpr (Drop::on) km = prob_keep_bits(dp, site, dp.pair0 + tb.row_pair[r], h, tb.tok_pos[s], nk);
             float dsum = 0.f;
             for (int j = 0; j < nk; ++j) {
                 const float* v = QKV + (base + j) * QLD + 2 * RD + h * RDH;
                 float a = 0.f;
                 for (int d = 0; d < RDH; ++d) a = fmaf(go[d], v[d], a);
+                if constexpr (Drop::on) a = ((km >> j) & 1) ? a * dp.k.scale : 0.f;
                 ds[j] = a;
                 dsum = fmaf(pr[j], a, dsum);
             }
             for (int j = 0; j < nk; ++j) {
                 const float g = pr[j] * (ds[j] - dsum) * scale;
                 ds[j] = g;
+                if constexpr (Drop::on) pr[j] = ((km >> j) & 1) ? pr[j] * dp.k.scale : 0.f;
                 const float* k = QKV + (base + j) * QLD + RD + h * RDH;
 #pragma unroll
                 for (int d = 0; d < RDH; ++d) dq[d] = fmaf(g, k[d], dq[d]);
@@ -160,10 +217,13 @@ __device__ __forceinline__ void self_attention_bwd(const TileTab& tb, const floa
 }
 
 // ------------------------------------------------------------------------------------------------------------------- the tile
+template <class... D>      // D: nothing (eval mode) or DropPhilox
 __global__ __launch_bounds__(NT) void k_rsb_cond_tile(const float* __restrict__ P, ScoreOff off, float eps, int n_rows, int K,
                                                       const int64_t* __restrict__ tgt, const int64_t* __restrict__ tgt_len, int n_pair, int T,
                                                       const int* __restrict__ cum, int S, const float* __restrict__ dlogits,
-                                                      float* __restrict__ slab, int* __restrict__ slot_id, int* __restrict__ slot_pos) {
+                                                      float* __restrict__ slab, int* __restrict__ slot_id, int* __restrict__ slot_pos, D... dpa) {
+    const auto dp = pick_drop(dpa...);
+    using Drop = std::remove_const_t<decltype(dp)>;
     __shared__ TileTab tb;
     float* X = smem;                               // [64][XLD]
     float* Tt = X + TM * XLD;                      // [64][XLD]
@@ -180,15 +240,20 @@ __global__ __launch_bounds__(NT) void k_rsb_cond_tile(const float* __restrict__ 
     }
     embed_tile(P + off.o[T_E], P + off.o[T_P], X, tb);
     __syncthreads();
+    const TileRows rows{tb, dp.pair0};
+    if constexpr (Drop::on) {
+        drop_tile<RD>(dp, DR4SR_REGEN_SITE_TGT_EMB, X, XLD, rows);
+        __syncthreads();
+    }
     const float scale = rsqrtf((float)RDH);
     // ---- the forward of k_rs_tile<0>, keeping what the backward reads (row r of the tile's pooling sits in record r)
     const KeepRec keep{rec, TOKF, TM};
     for (int l = 0; l < RNL; ++l) {
         const int64_t* lo = off.o + T_CENC + 12 * l;
         const int f = l * LF;
-        self_block_fwd(keep, {f + F_X, f + F_QKV, f + F_O, f + F_V1}, P, lo, E_INW, E_OUTW, E_N1W, eps, X, Tt, U,
-                       [&] { self_attention(tb, U, PS, Tt, scale); });
-        ffn_block_fwd(keep, {f + F_X1, f + F_HP, f + F_HH, f + F_V2}, P, lo, E_W1, E_W2, E_N2W, eps, X, Tt, U);
+        self_block_fwd(keep, dp, rs_site(ST_COND, l, 0), rows, {f + F_X, f + F_QKV, f + F_O, f + F_V1}, P, lo, E_INW, E_OUTW, E_N1W, eps, X, Tt, U,
+                       [&] { self_attention(dp, rs_site(ST_COND, l, 0), tb, U, PS, Tt, scale); });
+        ffn_block_fwd(keep, dp, rs_site(ST_COND, l, 2), rows, {f + F_X1, f + F_HP, f + F_HH, f + F_V2}, P, lo, E_W1, E_W2, E_N2W, eps, X, Tt, U);
     }
     pool_and_hidden(tb, n_row, tgt_len, P, off, X, Tt, U);
     keep.save(Tt, XLD, F_POOL, RD);
@@ -223,13 +288,23 @@ __global__ __launch_bounds__(NT) void k_rsb_cond_tile(const float* __restrict__ 
         const int f = l * LF;
         ln_bwd64(X, rec, f + F_V2, P + lo[E_N2W], eps, f + F_G2, f + F_Y2, f + F_DV2);
         __syncthreads();
-        gemm_dx<RD, 4>(X, XLD, P + lo[E_W2], U, FLD);
+        if constexpr (Drop::on) {          // DS is free between two attention blocks: the dropped gradient is the linear's dY
+            drop_grad64(dp, rs_site(ST_COND, l, 3), rows, X, DS, rec, TOKF, f + F_DV2, TM);
+            __syncthreads();
+            gemm_dx<RD, 4>(DS, XLD, P + lo[E_W2], U, FLD);
+        } else {
+            gemm_dx<RD, 4>(X, XLD, P + lo[E_W2], U, FLD);
+        }
         __syncthreads();
-        for (int e = threadIdx.x; e < TM * RF; e += NT) {
-            const int s = e / RF, c = e % RF;
-            const float d = U[s * FLD + c] * gelu_grad_exact(rec[(size_t)s * TOKF + f + F_HP + c]);
-            U[s * FLD + c] = d;
-            rec[(size_t)s * TOKF + f + F_DHP + c] = d;
+        if constexpr (Drop::on) {
+            gelu_bwd64(dp, rs_site(ST_COND, l, 2), rows, U, rec, TOKF, f + F_HP, f + F_DHP, TM);
+        } else {
+            for (int e = threadIdx.x; e < TM * RF; e += NT) {
+                const int s = e / RF, c = e % RF;
+                const float d = U[s * FLD + c] * gelu_grad_exact(rec[(size_t)s * TOKF + f + F_HP + c]);
+                U[s * FLD + c] = d;
+                rec[(size_t)s * TOKF + f + F_DHP + c] = d;
+            }
         }
         __syncthreads();
         gemm_dx<RF, 1>(U, FLD, P + lo[E_W1], Tt, XLD);
@@ -238,16 +313,26 @@ __global__ __launch_bounds__(NT) void k_rsb_cond_tile(const float* __restrict__ 
         __syncthreads();
         ln_bwd64(X, rec, f + F_V1, P + lo[E_N1W], eps, f + F_G1, f + F_Y1, f + F_DV1);
         __syncthreads();
-        gemm_dx<RD, 1>(X, XLD, P + lo[E_OUTW], Tt, XLD);
+        if constexpr (Drop::on) {
+            drop_grad64(dp, rs_site(ST_COND, l, 1), rows, X, DS, rec, TOKF, f + F_DV1, TM);
+            __syncthreads();
+            gemm_dx<RD, 1>(DS, XLD, P + lo[E_OUTW], Tt, XLD);
+        } else {
+            gemm_dx<RD, 1>(X, XLD, P + lo[E_OUTW], Tt, XLD);
+        }
         load64(U, QLD, rec, f + F_QKV, 3 * RD);
         __syncthreads();
-        self_attention_bwd(tb, U, Tt, PS, DS, rec + f + F_DQKV, scale);
+        self_attention_bwd(dp, rs_site(ST_COND, l, 0), tb, U, Tt, PS, DS, rec + f + F_DQKV, scale);
         __syncthreads();
         load64(U, QLD, rec, f + F_DQKV, 3 * RD);
         __syncthreads();
         gemm_dx<3 * RD, 1>(U, QLD, P + lo[E_INW], Tt, XLD);
         __syncthreads();
         for (int e = threadIdx.x; e < TM * RD; e += NT) X[(e / RD) * XLD + e % RD] += Tt[(e / RD) * XLD + e % RD];
+        __syncthreads();
+    }
+    if constexpr (Drop::on) {              // both embedding terms went through the tgt_emb mask: so does their gradient
+        drop_tile<RD>(dp, DR4SR_REGEN_SITE_TGT_EMB, X, XLD, rows);
         __syncthreads();
     }
     for (int e = threadIdx.x; e < TM * RD; e += NT) {
@@ -268,8 +353,10 @@ static_assert(R_Y3 + 64 == LFD && TOKD % 4 == 0, "decoder slot record layout");
 constexpr int KVW = RNL * 2 * RD;      // floats per (row, source position) of the mixed-memory gradient: [layer][K | V]
 
 // backward of the cross-attention: Q and dO [64][XLD] in LDS, PS holds the probabilities -> dQ [64][XLD] in LDS and the gradient of
-// the row's mixed K | V into dkv[row][j][layer][K | V] (zero where the key is masked or beyond the source)
-__device__ __forceinline__ void cross_bwd(const TileTab& tb, int n_row, int K, int Ls, int n_rows, int n_pair, int l, const int64_t* __restrict__ src,
+// the row's mixed K | V into dkv[row][j][layer][K | V] (zero where the key is masked or beyond the source).  Train mode: KM holds the keep
+// bits of every (slot, head) row (cross_probs): dV takes the dropped probabilities, DS = (dO . V) keep before the Jacobian on PS.
+template <class Drop>
+__device__ __forceinline__ void cross_bwd(const Drop& dp, const unsigned long long* KM, const TileTab& tb, int n_row, int K, int Ls, int n_rows, int n_pair, int l, const int64_t* __restrict__ src,
                                           const float* __restrict__ ckv, const float* __restrict__ cb, const float* Q, const float* dO,
                                           const float* PS, float* DS, float* DQ, float* __restrict__ dkv, float scale) {
     for (int e = threadIdx.x; e < n_row * RH * LMAX; e += NT) {
@@ -291,10 +378,16 @@ __device__ __forceinline__ void cross_bwd(const TileTab& tb, int n_row, int K, i
         for (int d = 0; d < RDH; ++d) dv[d] = 0.f;
         for (int t = 0; t < n; ++t) {
             const float* go = dO + (base + t) * XLD + h * RDH;
-            const float pj = PS[((base + t) * RH + h) * PLD + j];
+            float pj = PS[((base + t) * RH + h) * PLD + j];
+            bool kept = true;
+            if constexpr (Drop::on) {
+                kept = (KM[(base + t) * RH + h] >> j) & 1;
+                pj = kept ? pj * dp.k.scale : 0.f;
+            }
             float a = 0.f;
 #pragma unroll
             for (int d = 0; d < RDH; ++d) { a = fmaf(go[d], v[d], a); dv[d] = fmaf(pj, go[d], dv[d]); }
+            if constexpr (Drop::on) a = kept ? a * dp.k.scale : 0.f;
             DS[((base + t) * RH + h) * PLD + j] = a;
         }
 #pragma unroll
@@ -355,19 +448,23 @@ __device__ __forceinline__ void add64(float* X, const float* A) {
     for (int e = threadIdx.x; e < TM * RD; e += NT) X[(e / RD) * XLD + e % RD] += A[(e / RD) * XLD + e % RD];
 }
 
+template <class... D>      // D: nothing (eval mode) or DropPhilox
 __global__ __launch_bounds__(NT) void k_rsb_dec_tile(const float* __restrict__ P, ScoreOff off, float eps, int n_rows, int K,
                                                      const int64_t* __restrict__ src, const int64_t* __restrict__ src_len, int Ls,
                                                      const int64_t* __restrict__ tgt, const int64_t* __restrict__ tgt_len, int n_pair, int T,
                                                      const float* __restrict__ wts, int n_w, const int* __restrict__ cum, int S,
                                                      const float* __restrict__ ckv, const float* __restrict__ dnll, float* __restrict__ slab,
                                                      int* __restrict__ slot_id, int* __restrict__ slot_pos, float* __restrict__ dkv,
-                                                     float* __restrict__ delog, int* __restrict__ lkey) {
+                                                     float* __restrict__ delog, int* __restrict__ lkey, D... dpa) {
+    const auto dp = pick_drop(dpa...);
+    using Drop = std::remove_const_t<decltype(dp)>;
     __shared__ TileTab tb;
     float* X = smem;
     float* Tt = X + TM * XLD;
     float* U = Tt + TM * XLD;                      // [64][FLD]; in the cross-attention backward: q [64][XLD] then dq [64][XLD]
     float* PS = U + TM * FLD;
     float* DS = PS + TM * RH * PLD;
+    unsigned long long* KM = reinterpret_cast<unsigned long long*>(DS + TM * RH * PLD);     // [64][RH] keep bits; train mode only (DROP_KM_LDS)
     if (!build_tile_tab<1, true>(tb, n_rows, K, src_len, Ls, tgt, n_pair, T, wts, n_w, cum, S)) return;
     const int n_row = tb.n_row;
     float* rec = slab + (size_t)blockIdx.x * TM * TOKD;
@@ -379,16 +476,22 @@ __global__ __launch_bounds__(NT) void k_rsb_dec_tile(const float* __restrict__ P
     const float* E = P + off.o[T_E];
     embed_tile(E, P + off.o[T_P], X, tb);
     __syncthreads();
+    const TileRows rows{tb, dp.pair0};
+    if constexpr (Drop::on) {
+        drop_tile<RD>(dp, DR4SR_REGEN_SITE_TGT_EMB, X, XLD, rows);
+        __syncthreads();
+    }
     const float scale = rsqrtf((float)RDH);
     // ---- the forward of k_rs_tile<1>, keeping what the backward reads
     const KeepRec keep{rec, TOKD, TM};
     for (int l = 0; l < RNL; ++l) {
         const int64_t* lo = off.o + T_DEC + 18 * l;
         const int f = l * LFD;
-        self_block_fwd(keep, {f + R_X, f + R_QKV, f + R_O, f + R_V1}, P, lo, D_SAINW, D_SAOUTW, D_N1W, eps, X, Tt, U,
-                       [&] { self_attention(tb, U, PS, Tt, scale); });
-        cross_block_fwd(keep, {f + R_X1, f + R_QC, f + R_OC, f + R_V2}, tb, n_row, K, Ls, n_rows, l, src, ckv, P, lo, eps, X, Tt, U, PS, scale);
-        ffn_block_fwd(keep, {f + R_X2, f + R_HP, f + R_HH, f + R_V3}, P, lo, D_W1, D_W2, D_N3W, eps, X, Tt, U);
+        self_block_fwd(keep, dp, rs_site(ST_DEC, l, 0), rows, {f + R_X, f + R_QKV, f + R_O, f + R_V1}, P, lo, D_SAINW, D_SAOUTW, D_N1W, eps, X, Tt,
+                       U, [&] { self_attention(dp, rs_site(ST_DEC, l, 0), tb, U, PS, Tt, scale); });
+        cross_block_fwd(keep, dp, rs_site(ST_DEC, l, 2), rows, {f + R_X1, f + R_QC, f + R_OC, f + R_V2}, tb, n_row, K, Ls, n_rows, l, src, ckv, P,
+                        lo, eps, X, Tt, U, PS, scale);
+        ffn_block_fwd(keep, dp, rs_site(ST_DEC, l, 4), rows, {f + R_X2, f + R_HP, f + R_HH, f + R_V3}, P, lo, D_W1, D_W2, D_N3W, eps, X, Tt, U);
     }
     keep.save(X, XLD, R_VN, RD);
     __syncthreads();
@@ -438,13 +541,23 @@ __global__ __launch_bounds__(NT) void k_rsb_dec_tile(const float* __restrict__ P
         const int f = l * LFD;
         ln_bwd64(X, rec, f + R_V3, P + lo[D_N3W], eps, f + R_G3, f + R_Y3, f + R_DV3, TOKD);
         __syncthreads();
-        gemm_dx<RD, 4>(X, XLD, P + lo[D_W2], U, FLD);
+        if constexpr (Drop::on) {          // DS is free between two attention blocks: the dropped gradient is the linear's dY
+            drop_grad64(dp, rs_site(ST_DEC, l, 5), rows, X, DS, rec, TOKD, f + R_DV3, TM);
+            __syncthreads();
+            gemm_dx<RD, 4>(DS, XLD, P + lo[D_W2], U, FLD);
+        } else {
+            gemm_dx<RD, 4>(X, XLD, P + lo[D_W2], U, FLD);
+        }
         __syncthreads();
-        for (int e = threadIdx.x; e < TM * RF; e += NT) {
-            const int s = e / RF, c = e % RF;
-            const float d = U[s * FLD + c] * gelu_grad_exact(rec[(size_t)s * TOKD + f + R_HP + c]);
-            U[s * FLD + c] = d;
-            rec[(size_t)s * TOKD + f + R_DHP + c] = d;
+        if constexpr (Drop::on) {
+            gelu_bwd64(dp, rs_site(ST_DEC, l, 4), rows, U, rec, TOKD, f + R_HP, f + R_DHP, TM);
+        } else {
+            for (int e = threadIdx.x; e < TM * RF; e += NT) {
+                const int s = e / RF, c = e % RF;
+                const float d = U[s * FLD + c] * gelu_grad_exact(rec[(size_t)s * TOKD + f + R_HP + c]);
+                U[s * FLD + c] = d;
+                rec[(size_t)s * TOKD + f + R_DHP + c] = d;
+            }
         }
         __syncthreads();
         gemm_dx<RF, 1>(U, FLD, P + lo[D_W1], Tt, XLD);
@@ -454,13 +567,19 @@ __global__ __launch_bounds__(NT) void k_rsb_dec_tile(const float* __restrict__ P
         ln_bwd64(X, rec, f + R_V2, P + lo[D_N2W], eps, f + R_G2, f + R_Y2, f + R_DV2, TOKD);
         __syncthreads();
         // cross-attention: dO = dV2 Wo, then the probabilities again from the saved q
-        gemm_dx<RD, 1>(X, XLD, P + lo[D_CAOUTW], Tt, XLD);
+        if constexpr (Drop::on) {
+            drop_grad64(dp, rs_site(ST_DEC, l, 3), rows, X, DS, rec, TOKD, f + R_DV2, TM);
+            __syncthreads();
+            gemm_dx<RD, 1>(DS, XLD, P + lo[D_CAOUTW], Tt, XLD);
+        } else {
+            gemm_dx<RD, 1>(X, XLD, P + lo[D_CAOUTW], Tt, XLD);
+        }
         load64(U, XLD, rec, f + R_QC, RD, TOKD);
         __syncthreads();
         const float* cb = P + lo[D_CAINB];
-        cross_probs(tb, n_row, K, Ls, n_rows, l, src, ckv, cb, U, PS, scale);
+        cross_probs(dp, rs_site(ST_DEC, l, 2), KM, tb, n_row, K, Ls, n_rows, l, src, ckv, cb, U, PS, scale);
         float* DQ = U + TM * XLD;
-        cross_bwd(tb, n_row, K, Ls, n_rows, n_pair, l, src, ckv, cb, U, Tt, PS, DS, DQ, dkv, scale);
+        cross_bwd(dp, KM, tb, n_row, K, Ls, n_rows, n_pair, l, src, ckv, cb, U, Tt, PS, DS, DQ, dkv, scale);
         __syncthreads();
         keep.save(DQ, XLD, f + R_DQC, RD);
         gemm_dx<RD, 1>(DQ, XLD, P + lo[D_CAINW], Tt, XLD);
@@ -469,10 +588,16 @@ __global__ __launch_bounds__(NT) void k_rsb_dec_tile(const float* __restrict__ P
         __syncthreads();
         ln_bwd64(X, rec, f + R_V1, P + lo[D_N1W], eps, f + R_G1, f + R_Y1, f + R_DV1, TOKD);
         __syncthreads();
-        gemm_dx<RD, 1>(X, XLD, P + lo[D_SAOUTW], Tt, XLD);
+        if constexpr (Drop::on) {
+            drop_grad64(dp, rs_site(ST_DEC, l, 1), rows, X, DS, rec, TOKD, f + R_DV1, TM);
+            __syncthreads();
+            gemm_dx<RD, 1>(DS, XLD, P + lo[D_SAOUTW], Tt, XLD);
+        } else {
+            gemm_dx<RD, 1>(X, XLD, P + lo[D_SAOUTW], Tt, XLD);
+        }
         load64(U, QLD, rec, f + R_QKV, 3 * RD, TOKD);
         __syncthreads();
-        self_attention_bwd(tb, U, Tt, PS, DS, rec + f + R_DQKV, scale, TOKD);
+        self_attention_bwd(dp, rs_site(ST_DEC, l, 0), tb, U, Tt, PS, DS, rec + f + R_DQKV, scale, TOKD);
         __syncthreads();
         load64(U, QLD, rec, f + R_DQKV, 3 * RD, TOKD);
         __syncthreads();
@@ -481,11 +606,16 @@ __global__ __launch_bounds__(NT) void k_rsb_dec_tile(const float* __restrict__ P
         add64(X, Tt);
         __syncthreads();
     }
+    if constexpr (Drop::on) {              // both embedding terms went through the tgt_emb mask: so does their gradient
+        drop_tile<RD>(dp, DR4SR_REGEN_SITE_TGT_EMB, X, XLD, rows);
+        __syncthreads();
+    }
     for (int e = threadIdx.x; e < TM * RD; e += NT) {
         const int s = e / RD, c = e % RD;
         rec[(size_t)s * TOKD + R_DX0 + c] = tb.tok_row[s] >= 0 ? X[s * XLD + c] : 0.f;
     }
 }
+constexpr size_t DROP_KM_LDS = sizeof(unsigned long long) * TM * RH;      // the decoder tile's keep bits, behind DS (train mode only)
 
 // dw[row][k] = <d(K | V) of the row's mixed memory, (K | V)_k of its pair>: a wave per row, lane = feature, fixed order
 __global__ __launch_bounds__(256) void k_rsb_dw(const float* __restrict__ dkv, const float* __restrict__ ckv, int K, int n_pair, int n_w, int Ls,
@@ -516,11 +646,13 @@ constexpr int S_VN = RNL * LF, S_GN = S_VN + 64, S_YN = S_GN + 64, S_MEMN = S_YN
 static_assert(TOKS % 4 == 0, "source record layout");
 constexpr int ALD = 2 * RD + 4;
 
-template <int KC>
+template <int KC, class... D>      // D: nothing (eval mode) or DropPhilox
 __global__ __launch_bounds__(NT) void k_rsb_source(const float* __restrict__ P, ScoreOff off, float eps, int n_rows,
                                                    const int64_t* __restrict__ src, const int64_t* __restrict__ src_len, int Ls, int causal,
                                                    const float* __restrict__ wts, int n_w, int n_pair, const float* __restrict__ dkv,
-                                                   float* __restrict__ slab, int* __restrict__ key_id, int* __restrict__ key_pos) {
+                                                   float* __restrict__ slab, int* __restrict__ key_id, int* __restrict__ key_pos, D... dpa) {
+    const auto dp = pick_drop(dpa...);
+    using Drop = std::remove_const_t<decltype(dp)>;
     constexpr int KD = KC * RD, CLD = KD + 4;
     float* X = smem;                               // [64][XLD]
     float* T = X + TM * XLD;                       // [64][XLD]
@@ -539,6 +671,12 @@ __global__ __launch_bounds__(NT) void k_rsb_source(const float* __restrict__ P, 
     }
     embed_rows(P + off.o[T_E], P + off.o[T_P], X, [&](int j, int& id, int& pos) { id = ids[j]; pos = j; return j < n; });
     __syncthreads();
+    const int64_t gpair = dp.pair0 + p;
+    const SrcRows rows{gpair, n};
+    if constexpr (Drop::on) {
+        drop_tile<RD>(dp, DR4SR_REGEN_SITE_SRC_EMB, X, XLD, rows);
+        __syncthreads();
+    }
     const float scale = rsqrtf((float)RDH);
     float* QKV = U;                                // [64][QLD]
     float* S = U + TM * QLD;                       // [RH][LMAX][LMAX]
@@ -548,9 +686,11 @@ __global__ __launch_bounds__(NT) void k_rsb_source(const float* __restrict__ P, 
     for (int l = 0; l < RNL; ++l) {
         const int64_t* lo = off.o + T_ENC + 12 * l;
         const int f = l * LF;
-        self_block_fwd(keep, {f + F_X, f + F_QKV, f + F_O, f + F_V1}, P, lo, E_INW, E_OUTW, E_N1W, eps, X, T, U,
-                       [&] { src_probs(QKV, S, ids, n, causal, scale); src_context(QKV, S, n, T); });
-        ffn_block_fwd(keep, {f + F_X1, f + F_HP, f + F_HH, f + F_V2}, P, lo, E_W1, E_W2, E_N2W, eps, X, T, U);
+        self_block_fwd(keep, dp, rs_site(ST_SRC, l, 0), rows, {f + F_X, f + F_QKV, f + F_O, f + F_V1}, P, lo, E_INW, E_OUTW, E_N1W, eps, X, T, U, [&] {
+            src_probs(dp, rs_site(ST_SRC, l, 0), gpair, true, QKV, S, ids, n, causal, scale);
+            src_context(QKV, S, n, T);
+        });
+        ffn_block_fwd(keep, dp, rs_site(ST_SRC, l, 2), rows, {f + F_X1, f + F_HP, f + F_HH, f + F_V2}, P, lo, E_W1, E_W2, E_N2W, eps, X, T, U);
     }
     source_tail_fwd<KC>(keep, {S_VN, S_MEMN, S_C1}, P, off, eps, X, T, U, [&](int k) { keep.save(T, XLD, S_MEM + k * RD, RD); });
     // ---- backward.  d(K | V)_k of condition k = sum over the pair's weight vectors of w_k d(K | V), in vector order
@@ -602,13 +742,23 @@ __global__ __launch_bounds__(NT) void k_rsb_source(const float* __restrict__ P, 
         const int f = l * LF;
         ln_bwd64(X, rec, f + F_V2, P + lo[E_N2W], eps, f + F_G2, f + F_Y2, f + F_DV2, TOKS, Ls);
         __syncthreads();
-        gemm_dx<RD, 4>(X, XLD, P + lo[E_W2], U, FLD);
+        if constexpr (Drop::on) {          // T is free until the next GEMM fills it
+            drop_grad64(dp, rs_site(ST_SRC, l, 3), rows, X, T, rec, TOKS, f + F_DV2, Ls);
+            __syncthreads();
+            gemm_dx<RD, 4>(T, XLD, P + lo[E_W2], U, FLD);
+        } else {
+            gemm_dx<RD, 4>(X, XLD, P + lo[E_W2], U, FLD);
+        }
         __syncthreads();
-        for (int e = threadIdx.x; e < Ls * RF; e += NT) {
-            const int s = e / RF, c = e % RF;
-            const float d = U[s * FLD + c] * gelu_grad_exact(rec[(size_t)s * TOKS + f + F_HP + c]);
-            U[s * FLD + c] = d;
-            rec[(size_t)s * TOKS + f + F_DHP + c] = d;
+        if constexpr (Drop::on) {
+            gelu_bwd64(dp, rs_site(ST_SRC, l, 2), rows, U, rec, TOKS, f + F_HP, f + F_DHP, Ls);
+        } else {
+            for (int e = threadIdx.x; e < Ls * RF; e += NT) {
+                const int s = e / RF, c = e % RF;
+                const float d = U[s * FLD + c] * gelu_grad_exact(rec[(size_t)s * TOKS + f + F_HP + c]);
+                U[s * FLD + c] = d;
+                rec[(size_t)s * TOKS + f + F_DHP + c] = d;
+            }
         }
         __syncthreads();
         gemm_dx<RF, 1>(U, FLD, P + lo[E_W1], T, XLD);
@@ -617,10 +767,16 @@ __global__ __launch_bounds__(NT) void k_rsb_source(const float* __restrict__ P, 
         __syncthreads();
         ln_bwd64(X, rec, f + F_V1, P + lo[E_N1W], eps, f + F_G1, f + F_Y1, f + F_DV1, TOKS, Ls);
         __syncthreads();
-        gemm_dx<RD, 1>(X, XLD, P + lo[E_OUTW], T, XLD);              // dO
+        if constexpr (Drop::on) {          // S (behind q | k | v) is free until src_probs fills it
+            drop_grad64(dp, rs_site(ST_SRC, l, 1), rows, X, S, rec, TOKS, f + F_DV1, Ls);
+            __syncthreads();
+            gemm_dx<RD, 1>(S, XLD, P + lo[E_OUTW], T, XLD);
+        } else {
+            gemm_dx<RD, 1>(X, XLD, P + lo[E_OUTW], T, XLD);              // dO
+        }
         load64(QKV, QLD, rec, f + F_QKV, 3 * RD, TOKS, Ls);
         __syncthreads();
-        src_probs(QKV, S, ids, n, causal, scale);
+        src_probs(dp, rs_site(ST_SRC, l, 0), gpair, false, QKV, S, ids, n, causal, scale);
         for (int e = threadIdx.x; e < RH * n * n; e += NT) {
             const int h = e / (n * n), i = (e / n) % n, j = e % n;
             const float* go = T + i * XLD + h * RDH;
@@ -634,8 +790,21 @@ __global__ __launch_bounds__(NT) void k_rsb_source(const float* __restrict__ P, 
             const float* pr = S + ((e / n) * LMAX + e % n) * LMAX;
             float* ds = DSb + ((e / n) * LMAX + e % n) * LMAX;
             float dsum = 0.f;
-            for (int j = 0; j < n; ++j) dsum = fmaf(pr[j], ds[j], dsum);
-            for (int j = 0; j < n; ++j) ds[j] = pr[j] * (ds[j] - dsum) * scale;
+            if constexpr (Drop::on) {          // dP = (dO . V) keep; the Jacobian on the undropped p; S then takes the dropped p for dV
+                float* pw = S + ((e / n) * LMAX + e % n) * LMAX;
+                const uint64_t km = prob_keep_bits(dp, rs_site(ST_SRC, l, 0), gpair, e / n, e % n, n);
+                for (int j = 0; j < n; ++j) {
+                    ds[j] = ((km >> j) & 1) ? ds[j] * dp.k.scale : 0.f;
+                    dsum = fmaf(pr[j], ds[j], dsum);
+                }
+                for (int j = 0; j < n; ++j) {
+                    ds[j] = pr[j] * (ds[j] - dsum) * scale;
+                    pw[j] = ((km >> j) & 1) ? pr[j] * dp.k.scale : 0.f;
+                }
+            } else {
+                for (int j = 0; j < n; ++j) dsum = fmaf(pr[j], ds[j], dsum);
+                for (int j = 0; j < n; ++j) ds[j] = pr[j] * (ds[j] - dsum) * scale;
+            }
         }
         __syncthreads();
         for (int e = threadIdx.x; e < Ls * RD; e += NT) {
@@ -657,6 +826,10 @@ __global__ __launch_bounds__(NT) void k_rsb_source(const float* __restrict__ P, 
         gemm_dx<3 * RD, 1>(QKV, QLD, P + lo[E_INW], T, XLD);
         __syncthreads();
         add64(X, T);
+        __syncthreads();
+    }
+    if constexpr (Drop::on) {              // both embedding terms went through the src_emb mask: so does their gradient
+        drop_tile<RD>(dp, DR4SR_REGEN_SITE_SRC_EMB, X, XLD, rows);
         __syncthreads();
     }
     keep.save(X, XLD, S_DX0, RD);
@@ -829,14 +1002,18 @@ int zero_grad(const dr4sr_regen_plan* plan, float* grad, hipStream_t s) {
     return DR4SR_LAUNCH_CHECK();
 }
 
-template <int KC>
+template <int KC, class... D>
 int launch_bwd_source(const dr4sr_regen_plan* plan, const ScoreOff& off, const int64_t* src, const int64_t* src_len, int64_t n_pair, int Ls,
-                      int causal, const float* w, int n_w, const float* dkv, float* slab, int* sid, int* spos, hipStream_t s) {
-    big_lds(k_rsb_source<KC>, bwd_source_lds<KC>());
-    hipLaunchKernelGGL(k_rsb_source<KC>, dim3((unsigned)n_pair), dim3(NT), bwd_source_lds<KC>(), s, plan->params, off, plan->ln_eps, plan->n_rows,
-                       src, src_len, Ls, causal, w, n_w, (int)n_pair, dkv, slab, sid, spos);
+                      int causal, const float* w, int n_w, const float* dkv, float* slab, int* sid, int* spos, hipStream_t s, D... dp) {
+    big_lds(k_rsb_source<KC, D...>, bwd_source_lds<KC>());
+    hipLaunchKernelGGL((k_rsb_source<KC, D...>), dim3((unsigned)n_pair), dim3(NT), bwd_source_lds<KC>(), s, plan->params, off, plan->ln_eps,
+                       plan->n_rows, src, src_len, Ls, causal, w, n_w, (int)n_pair, dkv, slab, sid, spos, dp...);
     return DR4SR_LAUNCH_CHECK();
 }
+
+// the raw dropout arguments of a *_train entry point; the eval entry points pass none
+struct DropArgs { float p; uint64_t seed; uint32_t step; int64_t pair0; };
+int check_drop(float p, int64_t pair0) { return (p >= 0.f && p < 1.f && pair0 >= 0 && pair0 < (1LL << 40)) ? 0 : DR4SR_E_ARG; }
 
 }  // namespace
 
@@ -845,9 +1022,10 @@ extern "C" int64_t dr4sr_regen_score_condition_bwd_workspace_bytes(const dr4sr_r
     return cond_ws(plan, offsets_of(plan), n_pair, T).total;
 }
 
-extern "C" int dr4sr_regen_score_condition_bwd(const dr4sr_regen_plan* plan, const int64_t* tgt, const int64_t* tgt_len, int64_t n_pair, int32_t T,
-                                               const float* dlogits, void* workspace, int64_t workspace_bytes, float* grad, int32_t accumulate,
-                                               void* stream) {
+namespace {
+template <class... D>
+int condition_bwd(const dr4sr_regen_plan* plan, const int64_t* tgt, const int64_t* tgt_len, int64_t n_pair, int32_t T, const float* dlogits,
+                  void* workspace, int64_t workspace_bytes, float* grad, int32_t accumulate, void* stream, D... dp) {
     if (const int rc = check_sizes(plan, n_pair, 1, T, 1)) return rc;
     if (!tgt || !tgt_len || !dlogits || !grad) return DR4SR_E_ARG;
     const ScoreOff off = offsets_of(plan);
@@ -866,9 +1044,9 @@ extern "C" int dr4sr_regen_score_condition_bwd(const dr4sr_regen_plan* plan, con
     const int S = TM + 1 - T, K = plan->K;
     hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, s, tgt_len, (int)n_pair, T, 0, cum);
     if (const int rc = DR4SR_LAUNCH_CHECK()) return rc;
-    big_lds(k_rsb_cond_tile, BWD_TILE_LDS);
-    hipLaunchKernelGGL(k_rsb_cond_tile, dim3((unsigned)cond_tiles(n_pair, T)), dim3(NT), BWD_TILE_LDS, s, plan->params, off, plan->ln_eps,
-                       plan->n_rows, K, tgt, tgt_len, (int)n_pair, T, (const int*)cum, S, dlogits, slab, ids, pos);
+    big_lds(k_rsb_cond_tile<D...>, BWD_TILE_LDS);
+    hipLaunchKernelGGL((k_rsb_cond_tile<D...>), dim3((unsigned)cond_tiles(n_pair, T)), dim3(NT), BWD_TILE_LDS, s, plan->params, off, plan->ln_eps,
+                       plan->n_rows, K, tgt, tgt_len, (int)n_pair, T, (const int*)cum, S, dlogits, slab, ids, pos, dp...);
     if (const int rc = DR4SR_LAUNCH_CHECK()) return rc;
     WJobs js;
     js.n = 0; js.nblk = 0;
@@ -883,16 +1061,34 @@ extern "C" int dr4sr_regen_score_condition_bwd(const dr4sr_regen_plan* plan, con
     if (const int rc = launch_embed(plan->n_rows, slab, TOKF, F_DX0, ids, cum, n_pair, 1, S, -1, grad + off.o[T_E], s)) return rc;
     return launch_embed(LMAX, slab, TOKF, F_DX0, pos, cum, n_pair, 1, S, -1, grad + off.o[T_P], s);
 }
+}  // namespace
+
+extern "C" int dr4sr_regen_score_condition_bwd(const dr4sr_regen_plan* plan, const int64_t* tgt, const int64_t* tgt_len, int64_t n_pair, int32_t T,
+                                               const float* dlogits, void* workspace, int64_t workspace_bytes, float* grad, int32_t accumulate,
+                                               void* stream) {
+    return condition_bwd(plan, tgt, tgt_len, n_pair, T, dlogits, workspace, workspace_bytes, grad, accumulate, stream);
+}
+
+extern "C" int dr4sr_regen_score_condition_bwd_train(const dr4sr_regen_plan* plan, const int64_t* tgt, const int64_t* tgt_len, int64_t n_pair,
+                                                     int32_t T, const float* dlogits, void* workspace, int64_t workspace_bytes, float* grad,
+                                                     int32_t accumulate, float p, uint64_t seed, uint32_t step, int64_t pair0, void* stream) {
+    if (const int rc = check_drop(p, pair0)) return rc;
+    if (p == 0.f) return condition_bwd(plan, tgt, tgt_len, n_pair, T, dlogits, workspace, workspace_bytes, grad, accumulate, stream);
+    return condition_bwd(plan, tgt, tgt_len, n_pair, T, dlogits, workspace, workspace_bytes, grad, accumulate, stream,
+                         host_drop(p, seed, step, pair0));
+}
 
 extern "C" int64_t dr4sr_regen_score_bwd_workspace_bytes(const dr4sr_regen_plan* plan, int64_t n_pair, int32_t Ls, int32_t T, int32_t n_w) {
     if (const int rc = check_sizes(plan, n_pair, Ls, T, n_w)) return rc;
     return score_ws(plan, offsets_of(plan), n_pair, Ls, T, n_w).total;
 }
 
-extern "C" int dr4sr_regen_score_bwd(const dr4sr_regen_plan* plan, const int64_t* src, const int64_t* src_len, const int64_t* tgt,
-                                     const int64_t* tgt_len, int64_t n_pair, int32_t Ls, int32_t T, const float* w, int32_t n_w,
-                                     int32_t causal_source, const float* dnll, void* workspace, int64_t workspace_bytes, float* grad, float* dw,
-                                     float* nll_or_null, int32_t accumulate, void* stream) {
+namespace {
+// `da` (the raw arguments, for the forward's own entry point) and `dp` (the policy the kernels take) come together or not at all
+template <class... D>
+int score_bwd(const dr4sr_regen_plan* plan, const int64_t* src, const int64_t* src_len, const int64_t* tgt, const int64_t* tgt_len,
+              int64_t n_pair, int32_t Ls, int32_t T, const float* w, int32_t n_w, int32_t causal_source, const float* dnll, void* workspace,
+              int64_t workspace_bytes, float* grad, float* dw, float* nll_or_null, int32_t accumulate, void* stream, const DropArgs* da, D... dp) {
     if (const int rc = check_sizes(plan, n_pair, Ls, T, n_w)) return rc;
     if (!src || !src_len || !tgt || !tgt_len || !w || !dnll || !grad || !dw) return DR4SR_E_ARG;
     const ScoreOff off = offsets_of(plan);
@@ -918,18 +1114,22 @@ extern "C" int dr4sr_regen_score_bwd(const dr4sr_regen_plan* plan, const int64_t
     float* slab_s = reinterpret_cast<float*>(base + ws.slab_s);
     const int S = TM + 1 - T, K = plan->K;
     // the forward itself: the scan, every pair's K | V per condition and the NLLs stay in the first part of the workspace
-    if (const int rc = dr4sr_regen_score(plan, src, src_len, tgt, tgt_len, n_pair, Ls, T, w, n_w, causal_source, workspace,
-                                         ws_bytes(n_pair, K, Ls), nll, stream)) return rc;
-    big_lds(k_rsb_dec_tile, BWD_TILE_LDS);
-    hipLaunchKernelGGL(k_rsb_dec_tile, dim3((unsigned)ws.tiles), dim3(NT), BWD_TILE_LDS, s, plan->params, off, plan->ln_eps, plan->n_rows, K, src,
-                       src_len, Ls, tgt, tgt_len, (int)n_pair, T, w, n_w, (const int*)cum, S, (const float*)ckv, dnll, slab_d, ids, pos, dkv,
-                       delog, lkey);
+    if (const int rc = da ? dr4sr_regen_score_train(plan, src, src_len, tgt, tgt_len, n_pair, Ls, T, w, n_w, causal_source, workspace,
+                                                    ws_bytes(n_pair, K, Ls), nll, da->p, da->seed, da->step, da->pair0, stream)
+                          : dr4sr_regen_score(plan, src, src_len, tgt, tgt_len, n_pair, Ls, T, w, n_w, causal_source, workspace,
+                                              ws_bytes(n_pair, K, Ls), nll, stream)) return rc;
+    constexpr size_t dec_lds = BWD_TILE_LDS + (sizeof...(D) ? DROP_KM_LDS : 0);
+    big_lds(k_rsb_dec_tile<D...>, dec_lds);
+    hipLaunchKernelGGL((k_rsb_dec_tile<D...>), dim3((unsigned)ws.tiles), dim3(NT), dec_lds, s, plan->params, off, plan->ln_eps, plan->n_rows, K,
+                       src, src_len, Ls, tgt, tgt_len, (int)n_pair, T, w, n_w, (const int*)cum, S, (const float*)ckv, dnll, slab_d, ids, pos, dkv,
+                       delog, lkey, dp...);
     if (const int rc = DR4SR_LAUNCH_CHECK()) return rc;
     hipLaunchKernelGGL(k_rsb_dw, dim3((unsigned)((n_pair * n_w + 3) / 4)), dim3(256), 0, s, (const float*)dkv, (const float*)ckv, K, (int)n_pair,
                        n_w, Ls, dw);
     if (const int rc = DR4SR_LAUNCH_CHECK()) return rc;
     int rc = with_kc(K, [&](auto kc) {
-        return launch_bwd_source<decltype(kc)::value>(plan, off, src, src_len, n_pair, Ls, causal_source != 0, w, n_w, dkv, slab_s, sid, spos, s);
+        return launch_bwd_source<decltype(kc)::value, D...>(plan, off, src, src_len, n_pair, Ls, causal_source != 0, w, n_w, dkv, slab_s, sid, spos,
+                                                            s, dp...);
     });
     if (rc) return rc;
     const int64_t pb = off.o[T_ENC];
@@ -978,4 +1178,27 @@ extern "C" int dr4sr_regen_score_bwd(const dr4sr_regen_plan* plan, const int64_t
     if ((rc = launch_embed(plan->n_rows, delog, RD, 0, lkey, cum, n_pair, n_w, S, n_pair * n_w * Ls, gE, s))) return rc;
     if ((rc = launch_embed(LMAX, slab_d, TOKD, R_DX0, pos, cum, n_pair, n_w, S, -1, gP, s))) return rc;
     return launch_embed(LMAX, slab_s, TOKS, S_DX0, spos, cum, n_pair, n_w, S, n_pair * Ls, gP, s);
+}
+}  // namespace
+
+extern "C" int dr4sr_regen_score_bwd(const dr4sr_regen_plan* plan, const int64_t* src, const int64_t* src_len, const int64_t* tgt,
+                                     const int64_t* tgt_len, int64_t n_pair, int32_t Ls, int32_t T, const float* w, int32_t n_w,
+                                     int32_t causal_source, const float* dnll, void* workspace, int64_t workspace_bytes, float* grad, float* dw,
+                                     float* nll_or_null, int32_t accumulate, void* stream) {
+    return score_bwd(plan, src, src_len, tgt, tgt_len, n_pair, Ls, T, w, n_w, causal_source, dnll, workspace, workspace_bytes, grad, dw,
+                     nll_or_null, accumulate, stream, nullptr);
+}
+
+extern "C" int dr4sr_regen_score_bwd_train(const dr4sr_regen_plan* plan, const int64_t* src, const int64_t* src_len, const int64_t* tgt,
+                                           const int64_t* tgt_len, int64_t n_pair, int32_t Ls, int32_t T, const float* w, int32_t n_w,
+                                           int32_t causal_source, const float* dnll, void* workspace, int64_t workspace_bytes, float* grad,
+                                           float* dw, float* nll_or_null, int32_t accumulate, float p, uint64_t seed, uint32_t step, int64_t pair0,
+                                           void* stream) {
+    if (const int rc = check_drop(p, pair0)) return rc;
+    if (p == 0.f)
+        return score_bwd(plan, src, src_len, tgt, tgt_len, n_pair, Ls, T, w, n_w, causal_source, dnll, workspace, workspace_bytes, grad, dw,
+                         nll_or_null, accumulate, stream, nullptr);
+    const DropArgs da{p, seed, step, pair0};
+    return score_bwd(plan, src, src_len, tgt, tgt_len, n_pair, Ls, T, w, n_w, causal_source, dnll, workspace, workspace_bytes, grad, dw,
+                     nll_or_null, accumulate, stream, &da, host_drop(p, seed, step, pair0));
 }

@@ -24,6 +24,42 @@ enum { D_SAINW, D_SAINB, D_SAOUTW, D_SAOUTB, D_CAINW, D_CAINB, D_CAOUTW, D_CAOUT
 
 struct ScoreOff { int64_t o[DR4SR_REGEN_SCORE_TENSORS]; };
 
+// ------------------------------------------------------------------------------------------------------------------- dropout
+// The DROP policy every piece of the forward and of the backward is templated on:
+//   DropNone    eval mode: no site exists, nothing is generated (the kernels take no dropout argument at all).
+//   DropPhilox  train mode: the keep factor (0 or 1 / (1 - p)) of nn.Transformer's 30 sites, regenerated wherever it is consumed from
+//               (seed, step, site, element index) with common.h's 16-bit decisions (8 per Philox call).
+// Sites: rs_site(stack, layer, kind) and the two embedding sites (DR4SR_REGEN_SITE_* in include/dr4sr_hip.h; DESIGN.md has the table).
+// Element index (64-bit; fixed strides that depend on neither Ls, T, the tile nor the chunk), pair = pair0 + the call's pair:
+//   hidden sites  (pair 64 + position) 64 + column        FFN hidden  (pair 64 + position) 256 + column
+//   probabilities ((pair 2 + head) 64 + query position) 64 + key position
+// Host mirror, bit for bit: dr4sr_amd/regen_dropout.py.
+struct DropNone { static constexpr bool on = false; static constexpr int64_t pair0 = 0; };
+struct DropPhilox { static constexpr bool on = true; RngKey k; int64_t pair0; };
+__device__ __forceinline__ DropNone pick_drop() { return DropNone(); }
+__device__ __forceinline__ DropPhilox pick_drop(const DropPhilox& d) { return d; }
+
+enum { ST_SRC = 0, ST_COND = 1, ST_DEC = 2 };
+constexpr uint32_t rs_site(int stack, int layer, int kind) { return DR4SR_REGEN_SITE_BASE + stack * 32 + layer * 8 + kind; }
+
+DropPhilox host_drop(float p, uint64_t seed, uint32_t step, int64_t pair0) {      // make_rng of common.h on the host
+    DropPhilox d;
+    d.k.seed_lo = (uint32_t)seed; d.k.seed_hi = (uint32_t)(seed >> 32); d.k.step = step; d.k.p = p;
+    d.k.scale = 1.0f / (1.0f - p);
+    const float t = p * 65536.0f + 0.5f;
+    d.k.thresh = t >= 65535.0f ? 65535u : (uint32_t)t;
+    d.pair0 = pair0;
+    return d;
+}
+
+// the keep decisions of key positions 0 .. n - 1 (n <= 56) of the probability row (pair, head h, query position i): bit j = key j is kept
+__device__ __forceinline__ uint64_t prob_keep_bits(const DropPhilox& dp, uint32_t site, int64_t pair, int h, int i, int n) {
+    const uint64_t e0 = (uint64_t)(((pair * 2 + h) * 64 + i) * 64);
+    uint64_t m = 0;
+    for (int j = 0; j < n; j += 8) m |= (uint64_t)drop_bits8(dp.k, site, e0 + j) << j;
+    return m;
+}
+
 int64_t score_layout(int32_t n_rows, int32_t K, int64_t* off) {
     int64_t pos = dr4sr_regen_param_layout(n_rows, K, off);
     int i = DR4SR_REGEN_TENSORS;
@@ -77,7 +113,9 @@ struct TileTab {
 };
 
 // causal self-attention of every live slot over its own row's earlier slots (keys with id 0 masked); QKV [64][QLD] -> O [64][XLD]
-__device__ __forceinline__ void self_attention(const TileTab& tb, const float* QKV, float* PS, float* O, float scale) {
+// (train mode: P . V takes the dropped probabilities of `site`)
+template <class Drop>
+__device__ __forceinline__ void self_attention(const Drop& dp, uint32_t site, const TileTab& tb, const float* QKV, float* PS, float* O, float scale) {
     if (threadIdx.x < TM * RH) {
         const int s = threadIdx.x >> 1, h = threadIdx.x & 1, r = tb.tok_row[s];
         float acc[RDH];
@@ -98,8 +136,11 @@ __device__ __forceinline__ void self_attention(const TileTab& tb, const float* Q
                 pr[j] = v;
             }
             softmax_masked(pr, nk);
+            uint64_t km = 0;
+            if constexpr (Drop::on) km = prob_keep_bits(dp, site, dp.pair0 + tb.row_pair[r], h, tb.tok_pos[s], nk);
             for (int j = 0; j < nk; ++j) {
-                const float pj = pr[j];
+                float pj = pr[j];
+                if constexpr (Drop::on) pj = ((km >> j) & 1) ? pj * dp.k.scale : 0.f;
                 const float* v = QKV + (base + j) * QLD + 2 * RD + h * RDH;
 #pragma unroll
                 for (int d = 0; d < RDH; ++d) acc[d] = fmaf(pj, v[d], acc[d]);

@@ -5,7 +5,11 @@
 //   KeepRec    writes the activations into the slot records of the workspace: `rec` is the tile's (or the pair's) first record, `tf`
 //              the record stride in floats, `rows` the number of records that exist (64 for a tile, Ls for a source row).
 // A piece takes the record fields it would fill as a small struct of offsets; with KeepNone they are ignored ({} at the call).
-// Every float operation and its order is the same under both policies, with two exceptions that are kept as they were and marked
+// Next to it the DROP policy of regen_score_common.h: DropNone (eval mode; every piece is then what it was before the policy existed)
+// or DropPhilox (train mode: the keep factors of the reference's dropout sites, applied in LDS right behind the operation that the
+// reference drops, so the records KeepRec writes hold the post-dropout GEMM inputs).  `rows(s, pair, pos)` names the global pair and
+// the position of tile row s, false for a row that holds no token (no factor is generated for it).
+// Every float operation and its order is the same under both KEEP policies, with two exceptions that are kept as they were and marked
 // "KEPT DIFFERENCE" below; both leave the values bit-identical on every input the tests and tools/regen_bits.py know.
 #pragma once
 #include <type_traits>
@@ -35,6 +39,50 @@ struct SelfRec { int x, qkv, o, v; };      // a self-attention block: its input,
 struct CrossRec { int x, q, o, v; };       // the cross-attention block: its input, q, the attention output, the LayerNorm's input
 struct FfnRec { int x, hp, hh, v; };       // the FFN block: its input, the hidden layer before and after GELU, the LayerNorm's input
 struct TailRec { int vn, memn, c1; };      // the source tail: encoder.norm's input and output, condition_linear[0]'s output
+
+// the rows of a packed tile and of a source tile
+struct TileRows {
+    const TileTab& tb;
+    int64_t pair0;
+    __device__ __forceinline__ bool operator()(int s, int64_t& pair, int& pos) const {
+        const int r = tb.tok_row[s];
+        if (r < 0) return false;
+        pair = pair0 + tb.row_pair[r]; pos = tb.tok_pos[s];
+        return true;
+    }
+};
+struct SrcRows {
+    int64_t pair_;
+    int n;
+    __device__ __forceinline__ bool operator()(int s, int64_t& pair, int& pos) const {
+        if (s >= n) return false;
+        pair = pair_; pos = s;
+        return true;
+    }
+};
+
+__device__ __forceinline__ void mul8(float4& a, float4& b, const float4& lo, const float4& hi) {
+    a.x *= lo.x; a.y *= lo.y; a.z *= lo.z; a.w *= lo.w;
+    b.x *= hi.x; b.y *= hi.y; b.z *= hi.z; b.w *= hi.w;
+}
+
+// L[64][NC] *= the keep factors of `site` on the live rows: 8 columns per Philox call (NC = 64: a hidden site, 256: the FFN's)
+template <int NC, class Rows>
+__device__ __forceinline__ void drop_tile(const DropPhilox& dp, uint32_t site, float* L, int ld, const Rows& rows) {
+    constexpr int G = NC / 8;
+    for (int u = threadIdx.x; u < TM * G; u += NT) {
+        const int s = u / G, c0 = (u % G) * 8;
+        int64_t pair = 0;
+        int pos = 0;
+        if (!rows(s, pair, pos)) continue;
+        float4 lo, hi;
+        drop8(dp.k, site, (uint64_t)((pair * 64 + pos) * NC + c0), lo, hi);
+        float4* x = reinterpret_cast<float4*>(L + s * ld + c0);
+        float4 a = x[0], b = x[1];
+        mul8(a, b, lo, hi);
+        x[0] = a; x[1] = b;
+    }
+}
 
 __device__ __forceinline__ float gelu_exact(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 
@@ -154,9 +202,11 @@ __device__ __forceinline__ void embed_tile(const float* E, const float* Pos, flo
 // U are scratch.  Every block ends behind a barrier.
 
 // self-attention: attend() turns q | k | v in U [64][QLD] into the attention output in T
-template <class Keep, class Attend>
-__device__ __forceinline__ void self_block_fwd(const Keep& keep, SelfRec f, const float* P, const int64_t* lo, int inw, int outw, int nw,
-                                               float eps, float* X, float* T, float* U, Attend attend) {
+// (train mode: attend() drops the probabilities of site0 itself; the block drops its output, site0 + 1)
+template <class Keep, class Drop, class Rows, class Attend>
+__device__ __forceinline__ void self_block_fwd(const Keep& keep, const Drop& dp, uint32_t site0, const Rows& rows, SelfRec f, const float* P,
+                                               const int64_t* lo, int inw, int outw, int nw, float eps, float* X, float* T, float* U,
+                                               Attend attend) {
     keep.save(X, XLD, f.x, RD);
     gemm64<RD, 3, 0>(X, XLD, P + lo[inw], P + lo[inw + 1], U, QLD);
     __syncthreads();
@@ -166,19 +216,46 @@ __device__ __forceinline__ void self_block_fwd(const Keep& keep, SelfRec f, cons
     keep.save(T, XLD, f.o, RD);
     gemm64<RD, 1, 0>(T, XLD, P + lo[outw], P + lo[outw + 1], U, XLD);
     __syncthreads();
+    if constexpr (Drop::on) {
+        drop_tile<RD>(dp, site0 + 1, U, XLD, rows);
+        __syncthreads();
+    }
     add_ln64(keep, X, U, XLD, P + lo[nw], P + lo[nw + 1], eps, f.v);
     __syncthreads();
 }
 
 // KEPT DIFFERENCE: the scoring kernels apply GELU in the first GEMM's epilogue; the keeping kernels store the GEMM, then read it back to
 // keep the hidden layer before and after GELU.  The value is the same float expression on the same float either way.
-template <class Keep>
-__device__ __forceinline__ void ffn_block_fwd(const Keep& keep, FfnRec f, const float* P, const int64_t* lo, int w1, int w2, int nw,
-                                              float eps, float* X, float* T, float* U) {
+// Train mode drops the hidden layer behind GELU (site0; the record's f.hh holds the dropped values, the second GEMM's input) and the
+// block's output (site0 + 1).
+template <class Keep, class Drop, class Rows>
+__device__ __forceinline__ void ffn_block_fwd(const Keep& keep, const Drop& dp, uint32_t site0, const Rows& rows, FfnRec f, const float* P,
+                                              const int64_t* lo, int w1, int w2, int nw, float eps, float* X, float* T, float* U) {
     keep.save(X, XLD, f.x, RD);
     gemm64<RD, 4, Keep::on ? 0 : 2>(X, XLD, P + lo[w1], P + lo[w1 + 1], U, FLD);
     __syncthreads();
-    if constexpr (Keep::on) {
+    if constexpr (Keep::on && Drop::on) {
+        for (int u = threadIdx.x; u < TM * (RF / 8); u += NT) {
+            const int s = u / (RF / 8), c0 = (u % (RF / 8)) * 8;
+            int64_t pair = 0;
+            int pos = 0;
+            float4 lo4 = make_float4(1.f, 1.f, 1.f, 1.f), hi4 = lo4;
+            if (rows(s, pair, pos)) drop8(dp.k, site0, (uint64_t)((pair * 64 + pos) * RF + c0), lo4, hi4);
+            const float m[8] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float v = U[s * FLD + c0 + i];
+                const float g = gelu_exact(v) * m[i];
+                keep.put(s, f.hp + c0 + i, v);
+                keep.put(s, f.hh + c0 + i, g);
+                U[s * FLD + c0 + i] = g;
+            }
+        }
+        __syncthreads();
+    } else if constexpr (Drop::on) {
+        drop_tile<RF>(dp, site0, U, FLD, rows);
+        __syncthreads();
+    } else if constexpr (Keep::on) {
         for (int e = threadIdx.x; e < TM * RF; e += NT) {
             const int s = e / RF, c = e % RF;
             const float v = U[s * FLD + c];
@@ -191,6 +268,10 @@ __device__ __forceinline__ void ffn_block_fwd(const Keep& keep, FfnRec f, const 
     }
     gemm64<RF, 1, 0>(U, FLD, P + lo[w2], P + lo[w2 + 1], T, XLD);
     __syncthreads();
+    if constexpr (Drop::on) {
+        drop_tile<RD>(dp, site0 + 1, T, XLD, rows);
+        __syncthreads();
+    }
     add_ln64(keep, X, T, XLD, P + lo[nw], P + lo[nw + 1], eps, f.v);
     __syncthreads();
 }
@@ -221,9 +302,13 @@ __device__ __forceinline__ void mix_kv(const TileTab& tb, int r, int K, int Ls, 
     for (int d = 0; d < RDH; ++d) kv[d] += cb[RD + col + d];
 }
 
-// cross-attention probabilities of every live slot over its row's source positions (keys with id 0 masked); Q [64][XLD]
-__device__ __forceinline__ void cross_probs(const TileTab& tb, int n_row, int K, int Ls, int n_rows, int l, const int64_t* __restrict__ src,
-                                            const float* __restrict__ ckv, const float* __restrict__ cb, const float* Q, float* PS, float scale) {
+// cross-attention probabilities of every live slot over its row's source positions (keys with id 0 masked); Q [64][XLD].
+// Train mode: with KM null the probabilities are dropped in place (the forward: P . V takes the dropped ones); otherwise PS keeps the
+// softmax itself and KM[slot RH + h] takes the row's keep bits (the backward, whose softmax Jacobian needs the undropped ones).
+template <class Drop>
+__device__ __forceinline__ void cross_probs(const Drop& dp, uint32_t site, unsigned long long* KM, const TileTab& tb, int n_row, int K, int Ls,
+                                            int n_rows, int l, const int64_t* __restrict__ src, const float* __restrict__ ckv,
+                                            const float* __restrict__ cb, const float* Q, float* PS, float scale) {
     for (int e = threadIdx.x; e < n_row * RH * LMAX; e += NT) {
         const int r = e / (RH * LMAX), h = (e / LMAX) % RH, j = e % LMAX;
         const int base = tb.row_base[r], n = tb.row_n[r];
@@ -246,7 +331,16 @@ __device__ __forceinline__ void cross_probs(const TileTab& tb, int n_row, int K,
     __syncthreads();
     if (threadIdx.x < TM * RH) {
         const int r = tb.tok_row[threadIdx.x >> 1];
-        if (r >= 0) softmax_masked(PS + threadIdx.x * PLD, tb.row_ls[r]);
+        if (r >= 0) {
+            softmax_masked(PS + threadIdx.x * PLD, tb.row_ls[r]);
+            if constexpr (Drop::on) {
+                const int ls = tb.row_ls[r];
+                const uint64_t km = prob_keep_bits(dp, site, dp.pair0 + tb.row_pair[r], threadIdx.x & 1, tb.tok_pos[threadIdx.x >> 1], ls);
+                if (KM) KM[threadIdx.x] = km;
+                else
+                    for (int j = 0; j < ls; ++j) PS[threadIdx.x * PLD + j] = ((km >> j) & 1) ? PS[threadIdx.x * PLD + j] * dp.k.scale : 0.f;
+            }
+        }
     }
     __syncthreads();
 }
@@ -281,29 +375,36 @@ __device__ __forceinline__ void cross_out(const TileTab& tb, int n_row, int K, i
 }
 
 // the decoder layer's cross-attention over the row's mixed memory, K | V = sum_k w_k ckv_k + bias; PS [64][RH][PLD]
-template <class Keep>
-__device__ __forceinline__ void cross_block_fwd(const Keep& keep, CrossRec f, const TileTab& tb, int n_row, int K, int Ls, int n_rows, int l,
-                                                const int64_t* __restrict__ src, const float* __restrict__ ckv, const float* P,
-                                                const int64_t* lo, float eps, float* X, float* T, float* U, float* PS, float scale) {
+template <class Keep, class Drop, class Rows>
+__device__ __forceinline__ void cross_block_fwd(const Keep& keep, const Drop& dp, uint32_t site0, const Rows& rows, CrossRec f, const TileTab& tb,
+                                                int n_row, int K, int Ls, int n_rows, int l, const int64_t* __restrict__ src,
+                                                const float* __restrict__ ckv, const float* P, const int64_t* lo, float eps, float* X, float* T,
+                                                float* U, float* PS, float scale) {
     keep.save(X, XLD, f.x, RD);
     gemm64<RD, 1, 0>(X, XLD, P + lo[D_CAINW], P + lo[D_CAINB], U, XLD);
     __syncthreads();
     keep.save(U, XLD, f.q, RD);
     const float* cb = P + lo[D_CAINB];
-    cross_probs(tb, n_row, K, Ls, n_rows, l, src, ckv, cb, U, PS, scale);
+    cross_probs(dp, site0, nullptr, tb, n_row, K, Ls, n_rows, l, src, ckv, cb, U, PS, scale);
     cross_out(tb, n_row, K, Ls, l, ckv, cb, PS, T);
     __syncthreads();
     keep.save(T, XLD, f.o, RD);
     gemm64<RD, 1, 0>(T, XLD, P + lo[D_CAOUTW], P + lo[D_CAOUTB], U, XLD);
     __syncthreads();
+    if constexpr (Drop::on) {
+        drop_tile<RD>(dp, site0 + 1, U, XLD, rows);
+        __syncthreads();
+    }
     add_ln64(keep, X, U, XLD, P + lo[D_N2W], P + lo[D_N2B], eps, f.v);
     __syncthreads();
 }
 
 // ------------------------------------------------------------------------------------------------------------------- source side
 // the source encoder's attention probabilities S[h][i][j] of one pair's n live positions (causal as stage 2 trains or bidirectional as
-// stage 3 decodes; keys with id 0 masked); QKV [64][QLD]
-__device__ __forceinline__ void src_probs(const float* QKV, float* S, const int* ids, int n, int causal, float scale) {
+// stage 3 decodes; keys with id 0 masked); QKV [64][QLD].  Train mode with `apply`: dropped in place with the masks of (site, pair).
+template <class Drop>
+__device__ __forceinline__ void src_probs(const Drop& dp, uint32_t site, int64_t pair, bool apply, const float* QKV, float* S, const int* ids,
+                                          int n, int causal, float scale) {
     for (int e = threadIdx.x; e < RH * n * LMAX; e += NT) {
         const int h = e / (n * LMAX), i = (e / LMAX) % n, j = e % LMAX;
         float v = -INFINITY;
@@ -317,7 +418,16 @@ __device__ __forceinline__ void src_probs(const float* QKV, float* S, const int*
         S[(h * LMAX + i) * LMAX + j] = v;
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < RH * n; e += NT) softmax_masked(S + ((e / n) * LMAX + e % n) * LMAX, n);
+    for (int e = threadIdx.x; e < RH * n; e += NT) {
+        float* row = S + ((e / n) * LMAX + e % n) * LMAX;
+        softmax_masked(row, n);
+        if constexpr (Drop::on) {
+            if (apply) {
+                const uint64_t km = prob_keep_bits(dp, site, pair, e / n, e % n, n);
+                for (int j = 0; j < n; ++j) row[j] = ((km >> j) & 1) ? row[j] * dp.k.scale : 0.f;
+            }
+        }
+    }
     __syncthreads();
 }
 

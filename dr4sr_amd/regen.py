@@ -23,7 +23,8 @@ import os
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, regen_dropout
+from .regen_dropout import RegenDropout
 
 D, H, FF, N_LAYER, N_POS, MAX_LEN, LN_EPS = 64, 2, 256, 2, 50, 25, 1e-12
 NUM_ITEM = {"toy": 11925, "sport": 18358, "beauty": 12102, "yelp": 20034}     # 3.Hybrid_inference.py:237-242
@@ -387,10 +388,11 @@ class RegenModel:
             self._cast[key] = {k: v.to(device=device, dtype=dtype) for k, v in self.p.items()}
         return self._cast[key]
 
-    def _score_torch(self, src, tgt, tgt_len, w, want_cond, causal_source, dtype, params=None):
-        """Generator.forward + cross_entropy(reduction='none') of 2.Pretrain_regenerator.py in eval mode, batched, from the named
-        parameters: (nll [n_w, n, T] or None when w is None, condition logits [n, K] or None).  `params` (name -> tensor of `dtype` on
-        src's device) replaces the model's own: loss_and_grad passes leaves that require grad"""
+    def _score_torch(self, src, tgt, tgt_len, w, want_cond, causal_source, dtype, params=None, drop=None):
+        """Generator.forward + cross_entropy(reduction='none') of 2.Pretrain_regenerator.py, batched, from the named parameters:
+        (nll [n_w, n, T] or None when w is None, condition logits [n, K] or None).  `params` (name -> tensor of `dtype` on src's
+        device) replaces the model's own: loss_and_grad passes leaves that require grad.  drop=None is eval mode; a _TorchDrop is
+        train mode: the kernels' own masks (regen_dropout.py) at nn.Transformer's 30 dropout sites"""
         dev = src.device
         p = self._params_as(dtype, dev) if params is None else params
         E, P = p["item_embedding.weight"], p["position_embedding.weight"]
@@ -399,28 +401,33 @@ class RegenModel:
         tgt_in, tgt_out = tgt[:, :-1], tgt[:, 1:]
         ninf = float("-inf")
 
-        def mha(pre, xq, xkv, bias):
+        nodrop = drop is None
+        rows_ = (lambda x, s: x) if nodrop else (lambda x, s: x * drop.rows(s, x))
+        probs_ = (lambda a, s: a) if nodrop else (lambda a, s: a * drop.probs(s, a))
+
+        def mha(pre, xq, xkv, bias, st, l, kind):
             W, b = p[pre + ".in_proj_weight"], p[pre + ".in_proj_bias"]
             B, Lq, _ = xq.shape
             Lk = xkv.shape[1]
             q = F.linear(xq, W[:D], b[:D]).view(B, Lq, H, D // H).transpose(1, 2)
             k = F.linear(xkv, W[D:2 * D], b[D:2 * D]).view(B, Lk, H, D // H).transpose(1, 2)
             v = F.linear(xkv, W[2 * D:], b[2 * D:]).view(B, Lk, H, D // H).transpose(1, 2)
-            a = torch.softmax((q @ k.transpose(-1, -2)) / math.sqrt(D // H) + bias, -1)
-            return F.linear((a @ v).transpose(1, 2).reshape(B, Lq, D), p[pre + ".out_proj.weight"], p[pre + ".out_proj.bias"])
+            a = probs_(torch.softmax((q @ k.transpose(-1, -2)) / math.sqrt(D // H) + bias, -1), (st, l, kind))
+            return rows_(F.linear((a @ v).transpose(1, 2).reshape(B, Lq, D), p[pre + ".out_proj.weight"], p[pre + ".out_proj.bias"]),
+                         (st, l, kind + 1))
 
         def ln(x, pre):
             return F.layer_norm(x, (D,), p[pre + ".weight"], p[pre + ".bias"], LN_EPS)
 
-        def ffn(x, pre):
-            return F.linear(F.gelu(F.linear(x, p[pre + ".linear1.weight"], p[pre + ".linear1.bias"])),
-                            p[pre + ".linear2.weight"], p[pre + ".linear2.bias"])
+        def ffn(x, pre, st, l, kind):
+            hid = rows_(F.gelu(F.linear(x, p[pre + ".linear1.weight"], p[pre + ".linear1.bias"])), (st, l, kind))
+            return rows_(F.linear(hid, p[pre + ".linear2.weight"], p[pre + ".linear2.bias"]), (st, l, kind + 1))
 
-        def enc_layers(x, bias, stem):
+        def enc_layers(x, bias, stem, st):
             for i in range(N_LAYER):
                 pre = f"{stem}.layers.{i}"
-                x = ln(x + mha(pre + ".self_attn", x, x, bias), pre + ".norm1")
-                x = ln(x + ffn(x, pre), pre + ".norm2")
+                x = ln(x + mha(pre + ".self_attn", x, x, bias, st, i, 0), pre + ".norm1")
+                x = ln(x + ffn(x, pre, st, i, 2), pre + ".norm2")
             return x
 
         def key_bias(ids):
@@ -430,10 +437,10 @@ class RegenModel:
             return torch.full((L, L), ninf, dtype=dtype, device=dev).triu(1)
 
         tgt_kb = key_bias(tgt_in)
-        x_t = E[tgt_in] + P[:T]
+        x_t = rows_(E[tgt_in] + P[:T], "tgt_emb")
         cond = None
         if want_cond:
-            y = enc_layers(x_t, causal(T) + tgt_kb, "condition_encoder.encoder")
+            y = enc_layers(x_t, causal(T) + tgt_kb, "condition_encoder.encoder", regen_dropout.STACK_COND)
             keep = torch.arange(T, device=dev)[None, :] < tgt_len[:, None]
             pooled = (y * keep[:, :, None].to(dtype)).sum(1) / tgt_len[:, None].to(dtype)
             hid = torch.relu(F.linear(pooled, p["condition_encoder.condition_layer.0.weight"], p["condition_encoder.condition_layer.0.bias"]))
@@ -441,7 +448,8 @@ class RegenModel:
         if w is None:
             return None, cond
         src_kb = key_bias(src)
-        x = enc_layers(E[src] + P[:Ls], (causal(Ls) if causal_source else 0) + src_kb, "transformer.encoder")
+        x = enc_layers(rows_(E[src] + P[:Ls], "src_emb"), (causal(Ls) if causal_source else 0) + src_kb, "transformer.encoder",
+                       regen_dropout.STACK_SRC)
         mem = ln(x, "transformer.encoder.norm")
         c1 = torch.relu(F.linear(mem, p["condition_linear.0.weight"], p["condition_linear.0.bias"]))
         mem = F.linear(c1, p["condition_linear.2.weight"], p["condition_linear.2.bias"]).view(n, Ls, self.K, D)
@@ -455,9 +463,9 @@ class RegenModel:
             h = x_t
             for i in range(N_LAYER):
                 pre = f"transformer.decoder.layers.{i}"
-                h = ln(h + mha(pre + ".self_attn", h, h, dec_bias), pre + ".norm1")
-                h = ln(h + mha(pre + ".multihead_attn", h, mc, src_kb), pre + ".norm2")
-                h = ln(h + ffn(h, pre), pre + ".norm3")
+                h = ln(h + mha(pre + ".self_attn", h, h, dec_bias, regen_dropout.STACK_DEC, i, 0), pre + ".norm1")
+                h = ln(h + mha(pre + ".multihead_attn", h, mc, src_kb, regen_dropout.STACK_DEC, i, 2), pre + ".norm2")
+                h = ln(h + ffn(h, pre, regen_dropout.STACK_DEC, i, 4), pre + ".norm3")
             h = ln(h, "transformer.decoder.norm")
             lg = (h @ Es.transpose(1, 2)).masked_fill(dup[:, None, :], ninf)
             lse = torch.logsumexp(lg, -1)
@@ -466,9 +474,10 @@ class RegenModel:
             out.append(nll.masked_fill(tgt_out == 0, 0.0))
         return torch.stack(out), cond
 
-    def score_device(self, src, src_len, tgt, tgt_len, w, causal_source=True, workspace=None):
+    def score_device(self, src, src_len, tgt, tgt_len, w, causal_source=True, workspace=None, dropout=None, pair0=0):
         """the HIP call on device tensors (src [n, Ls], tgt [n, T + 1] int64, w [n_w, n, K] fp32): nll [n_w, n, T] on the device.
-        Only enqueues on the current stream (capturable); `workspace` may be reused between calls of the same sizes"""
+        Only enqueues on the current stream (capturable); `workspace` may be reused between calls of the same sizes.  dropout (a
+        RegenDropout) scores in train mode; row i then takes the masks of global pair pair0 + i"""
         lib = _lib.load()
         plan = self.score_plan()
         n, Ls = src.shape
@@ -480,13 +489,16 @@ class RegenModel:
         if workspace is None:
             workspace = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
         nll = torch.empty(n_w, n, T, dtype=torch.float32, device=self.device)
-        _lib.check(lib.dr4sr_regen_score(C.byref(plan), _lib.ptr(src), _lib.ptr(src_len), _lib.ptr(tgt), _lib.ptr(tgt_len), n, Ls, T,
-                                         _lib.ptr(w), n_w, int(bool(causal_source)), C.c_void_p(workspace.data_ptr()), workspace.numel(),
-                                         _lib.ptr(nll), _lib.cur_stream()), "dr4sr_regen_score")
+        args = (C.byref(plan), _lib.ptr(src), _lib.ptr(src_len), _lib.ptr(tgt), _lib.ptr(tgt_len), n, Ls, T, _lib.ptr(w), n_w,
+                int(bool(causal_source)), C.c_void_p(workspace.data_ptr()), workspace.numel(), _lib.ptr(nll))
+        if _eval_mode(dropout):
+            _lib.check(lib.dr4sr_regen_score(*args, _lib.cur_stream()), "dr4sr_regen_score")
+        else:
+            _lib.check(lib.dr4sr_regen_score_train(*args, *_drop_args(dropout, pair0), _lib.cur_stream()), "dr4sr_regen_score_train")
         return nll
 
-    def condition_device(self, tgt, tgt_len, workspace=None):
-        """condition logits [n, K] of the condition_encoder on device tensors (HIP; only enqueues)"""
+    def condition_device(self, tgt, tgt_len, workspace=None, dropout=None, pair0=0):
+        """condition logits [n, K] of the condition_encoder on device tensors (HIP; only enqueues); dropout / pair0 as score_device"""
         lib = _lib.load()
         plan = self.score_plan()
         n, T = tgt.shape[0], tgt.shape[1] - 1
@@ -496,8 +508,12 @@ class RegenModel:
         if workspace is None:
             workspace = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
         out = torch.empty(n, self.K, dtype=torch.float32, device=self.device)
-        _lib.check(lib.dr4sr_regen_score_condition(C.byref(plan), _lib.ptr(tgt), _lib.ptr(tgt_len), n, T, C.c_void_p(workspace.data_ptr()),
-                                                   workspace.numel(), _lib.ptr(out), _lib.cur_stream()), "dr4sr_regen_score_condition")
+        args = (C.byref(plan), _lib.ptr(tgt), _lib.ptr(tgt_len), n, T, C.c_void_p(workspace.data_ptr()), workspace.numel(), _lib.ptr(out))
+        if _eval_mode(dropout):
+            _lib.check(lib.dr4sr_regen_score_condition(*args, _lib.cur_stream()), "dr4sr_regen_score_condition")
+        else:
+            _lib.check(lib.dr4sr_regen_score_condition_train(*args, *_drop_args(dropout, pair0), _lib.cur_stream()),
+                       "dr4sr_regen_score_condition_train")
         return out
 
     # ------------------------------------------------------------------------------------------------ parameters in and out
@@ -546,7 +562,7 @@ class RegenModel:
                 out[name] = flat[off[i]:off[i] + math.prod(shape)].view(shape)
         return out
 
-    def condition_bwd_device(self, tgt, tgt_len, dlogits, grad=None, accumulate=False, workspace=None):
+    def condition_bwd_device(self, tgt, tgt_len, dlogits, grad=None, accumulate=False, workspace=None, dropout=None, pair0=0):
         """the HIP backward of condition_device on device tensors: dlogits [n, K] fp32 -> the flat gradient (98-tensor score layout;
         condition_encoder.* and the two tables receive values).  accumulate=False overwrites every element of `grad` (a new buffer
         when None), True adds to it.  Only enqueues on the current stream (capturable); the same inputs give the same bits"""
@@ -564,12 +580,17 @@ class RegenModel:
             grad = torch.empty(plan.n_params, dtype=torch.float32, device=self.device)
         if grad.numel() != plan.n_params or grad.dtype != torch.float32:
             raise ValueError(f"grad must hold {plan.n_params} fp32 values")
-        _lib.check(lib.dr4sr_regen_score_condition_bwd(C.byref(plan), _lib.ptr(tgt), _lib.ptr(tgt_len), n, T, _lib.ptr(dlogits),
-                                                       C.c_void_p(workspace.data_ptr()), workspace.numel(), _lib.ptr(grad),
-                                                       int(bool(accumulate)), _lib.cur_stream()), "dr4sr_regen_score_condition_bwd")
+        args = (C.byref(plan), _lib.ptr(tgt), _lib.ptr(tgt_len), n, T, _lib.ptr(dlogits), C.c_void_p(workspace.data_ptr()), workspace.numel(),
+                _lib.ptr(grad), int(bool(accumulate)))
+        if _eval_mode(dropout):
+            _lib.check(lib.dr4sr_regen_score_condition_bwd(*args, _lib.cur_stream()), "dr4sr_regen_score_condition_bwd")
+        else:
+            _lib.check(lib.dr4sr_regen_score_condition_bwd_train(*args, *_drop_args(dropout, pair0), _lib.cur_stream()),
+                       "dr4sr_regen_score_condition_bwd_train")
         return grad
 
-    def score_bwd_device(self, src, src_len, tgt, tgt_len, w, dnll, causal_source=True, grad=None, accumulate=False, workspace=None):
+    def score_bwd_device(self, src, src_len, tgt, tgt_len, w, dnll, causal_source=True, grad=None, accumulate=False, workspace=None,
+                         dropout=None, pair0=0):
         """the HIP backward of score_device on device tensors: dnll [n_w, n, T] fp32 -> (flat gradient in the 98-tensor score layout,
         dw [n_w, n, K], nll [n_w, n, T]).  Self-contained (runs the forward it needs); accumulate=False overwrites every element of
         `grad` (a new buffer when None), True adds.  Only enqueues on the current stream; the same inputs give the same bits"""
@@ -593,13 +614,16 @@ class RegenModel:
             raise ValueError(f"dnll of shape {tuple(dnll.shape)}, expected ({n_w}, {n}, {T})")
         dw = torch.empty(n_w, n, self.K, dtype=torch.float32, device=self.device)
         nll = torch.empty(n_w, n, T, dtype=torch.float32, device=self.device)
-        _lib.check(lib.dr4sr_regen_score_bwd(C.byref(plan), _lib.ptr(src), _lib.ptr(src_len), _lib.ptr(tgt), _lib.ptr(tgt_len), n, Ls, T,
-                                             _lib.ptr(w), n_w, int(bool(causal_source)), _lib.ptr(dnll), C.c_void_p(workspace.data_ptr()),
-                                             workspace.numel(), _lib.ptr(grad), _lib.ptr(dw), _lib.ptr(nll), int(bool(accumulate)),
-                                             _lib.cur_stream()), "dr4sr_regen_score_bwd")
+        args = (C.byref(plan), _lib.ptr(src), _lib.ptr(src_len), _lib.ptr(tgt), _lib.ptr(tgt_len), n, Ls, T, _lib.ptr(w), n_w,
+                int(bool(causal_source)), _lib.ptr(dnll), C.c_void_p(workspace.data_ptr()), workspace.numel(), _lib.ptr(grad), _lib.ptr(dw),
+                _lib.ptr(nll), int(bool(accumulate)))
+        if _eval_mode(dropout):
+            _lib.check(lib.dr4sr_regen_score_bwd(*args, _lib.cur_stream()), "dr4sr_regen_score_bwd")
+        else:
+            _lib.check(lib.dr4sr_regen_score_bwd_train(*args, *_drop_args(dropout, pair0), _lib.cur_stream()), "dr4sr_regen_score_bwd_train")
         return grad, dw, nll
 
-    def _loss_and_grad_hip(self, src, src_len, tgt, tgt_len, T, conditions, causal_source, noise, tau, entropy_weight):
+    def _loss_and_grad_hip(self, src, src_len, tgt, tgt_len, T, conditions, causal_source, noise, tau, entropy_weight, dropout=None, pair0=0):
         dev = self.device
         n = src.shape[0]
         encoder = isinstance(conditions, str)
@@ -612,7 +636,7 @@ class RegenModel:
             b = min(n, a + SCORE_BWD_PAIRS_PER_CALL)
             s_d, sl_d = src[a:b].to(dev).contiguous(), src_len[a:b].to(dev).contiguous()
             t_d, tl_d = tgt[a:b].to(dev).contiguous(), tgt_len[a:b].to(dev).contiguous()
-            c = self.condition_device(t_d, tl_d) if self.has_condition_encoder else None
+            c = self.condition_device(t_d, tl_d, None, dropout, pair0 + a) if self.has_condition_encoder else None
             if encoder:                  # the few [n, K] operations between dw and the condition encoder's backward: torch autograd
                 c_leaf = c.detach().requires_grad_(True)
                 z = c_leaf if noise is None else c_leaf + torch.as_tensor(noise)[a:b].to(dev, torch.float32)
@@ -622,12 +646,13 @@ class RegenModel:
             else:
                 w = conditions[:, a:b].to(dev, torch.float32).contiguous()
             dnll = torch.full((w.shape[0], b - a, T), 1.0 / n_tok, dtype=torch.float32, device=dev)
-            flat, dw, nll = self.score_bwd_device(s_d, sl_d, t_d, tl_d, w, dnll, causal_source, flat, accumulate=flat is not None)
+            flat, dw, nll = self.score_bwd_device(s_d, sl_d, t_d, tl_d, w, dnll, causal_source, flat, accumulate=flat is not None,
+                                                  dropout=dropout, pair0=pair0 + a)
             loss += float(nll.double().sum()) / n_tok
             if encoder:
                 entropy += float(ent.detach())
                 (dlog,) = torch.autograd.grad((w0 * dw[0]).sum() + entropy_weight * ent, c_leaf)
-                self.condition_bwd_device(t_d, tl_d, dlog.contiguous(), flat, accumulate=True)
+                self.condition_bwd_device(t_d, tl_d, dlog.contiguous(), flat, accumulate=True, dropout=dropout, pair0=pair0 + a)
             dws.append(dw)
             if c is not None:
                 conds.append(c)
@@ -637,7 +662,7 @@ class RegenModel:
         return GradResult(loss, entropy if encoder else None, self.grads_from_flat(flat),
                           torch.cat(dws, 1) if dws else torch.zeros(n_w, 0, self.K, device=dev), torch.cat(conds) if conds else None)
 
-    def condition_grad(self, pairs, dlogits, width=None, backend: str = "hip", dtype=torch.float32):
+    def condition_grad(self, pairs, dlogits, width=None, backend: str = "hip", dtype=torch.float32, dropout=None, pair0: int = 0):
         """gradients of sum(cond_logits * dlogits) over the given pairs: state-dict name -> tensor for condition_encoder.* and the
         two tables (the vector-Jacobian product of score()'s cond_logits).  backend="hip" runs csrc/regen_score_bwd.hip, chunked
         with `accumulate`; backend="torch" is autograd through the eager restatement in `dtype`"""
@@ -657,19 +682,22 @@ class RegenModel:
             for a in range(0, max(n, 1), COND_BWD_PAIRS_PER_CALL):
                 b = min(n, a + COND_BWD_PAIRS_PER_CALL)
                 flat = self.condition_bwd_device(tgt[a:b].to(dev).contiguous(), tgt_len[a:b].to(dev).contiguous(),
-                                                 dlogits[a:b].to(dev, torch.float32).contiguous(), flat, accumulate=flat is not None)
+                                                 dlogits[a:b].to(dev, torch.float32).contiguous(), flat, accumulate=flat is not None,
+                                                 dropout=dropout, pair0=pair0 + a)
             g = self.grads_from_flat(flat)
             return {k: g[k] for k in names}
         leaves = {k: v.to(device=dev, dtype=dtype).clone().requires_grad_(k in names) for k, v in self.p.items()}
         for a in range(0, n, ROWS_PER_TORCH):
             b = min(n, a + ROWS_PER_TORCH)
-            _, c = self._score_torch(tgt[a:b, :1].to(dev), tgt[a:b].to(dev), tgt_len[a:b].to(dev), None, True, True, dtype, leaves)
+            _, c = self._score_torch(tgt[a:b, :1].to(dev), tgt[a:b].to(dev), tgt_len[a:b].to(dev), None, True, True, dtype, leaves,
+                                     _TorchDrop.of(dropout, pair0 + a, b - a, dtype, dev))
             (c * dlogits[a:b].to(dev, dtype)).sum().backward()
         return {k: (leaves[k].grad if leaves[k].grad is not None else torch.zeros_like(leaves[k])) for k in names}
 
     def loss_and_grad(self, pairs, conditions, causal_source: bool = True, width=None, backend: str = "hip", dtype=torch.float32,
-                      noise=None, tau: float = 1.0, entropy_weight: float = 0.0):
-        """The reference's training loss in eval mode and its gradient with respect to every parameter.
+                      noise=None, tau: float = 1.0, entropy_weight: float = 0.0, dropout=None, pair0: int = 0):
+        """The reference's training loss and its gradient with respect to every parameter: in eval mode (dropout=None), or in train
+        mode with the masks a RegenDropout names (pair i takes the masks of global pair pair0 + i, whatever the chunking).
 
         loss: CrossEntropyLoss(ignore_index=0) over ALL given pairs as one batch, per weight vector and summed over them.
         conditions: a [n_w, n, K] tensor (a constant; `dw` is the loss's gradient with respect to it) or "encoder":
@@ -701,7 +729,8 @@ class RegenModel:
             if conditions.dim() != 3 or tuple(conditions.shape[1:]) != (n, self.K):
                 raise ValueError(f"condition weights of shape {tuple(conditions.shape)}, expected [n_w, {n}, {self.K}]")
         if backend == "hip":
-            return self._loss_and_grad_hip(src, src_len, tgt, tgt_len, T, conditions, causal_source, noise, tau, entropy_weight)
+            return self._loss_and_grad_hip(src, src_len, tgt, tgt_len, T, conditions, causal_source, noise, tau, entropy_weight, dropout,
+                                           int(pair0))
         dev = self.device
         n_tok = max(int((tgt[:, 1:] != 0).sum()), 1)
         leaves = {k: v.to(device=dev, dtype=dtype).clone().requires_grad_(True) for k, v in self.p.items()}
@@ -712,8 +741,9 @@ class RegenModel:
             b = min(n, a + ROWS_PER_TORCH)
             s_d, t_d, tl_d = src[a:b].to(dev), tgt[a:b].to(dev), tgt_len[a:b].to(dev)
             ent = None
+            td = _TorchDrop.of(dropout, int(pair0) + a, b - a, dtype, dev)
             if encoder:
-                _, c = self._score_torch(s_d, t_d, tl_d, None, True, causal_source, dtype, leaves)
+                _, c = self._score_torch(s_d, t_d, tl_d, None, True, causal_source, dtype, leaves, td)
                 z = c if noise is None else c + torch.as_tensor(noise)[a:b].to(dev, dtype)
                 w0 = torch.softmax(z / tau, -1)
                 ent = -(w0 * torch.log(w0 + 1e-12)).sum(-1).sum() / n
@@ -722,7 +752,7 @@ class RegenModel:
                 c = None
                 w = conditions[:, a:b].to(dev, dtype).clone().requires_grad_(True)
             w.retain_grad()
-            nll, c2 = self._score_torch(s_d, t_d, tl_d, w, self.has_condition_encoder and c is None, causal_source, dtype, leaves)
+            nll, c2 = self._score_torch(s_d, t_d, tl_d, w, self.has_condition_encoder and c is None, causal_source, dtype, leaves, td)
             ce = nll.sum() / n_tok
             (ce if ent is None else ce + entropy_weight * ent).backward()
             loss += float(ce.detach())
@@ -739,17 +769,19 @@ class RegenModel:
                           torch.cat(conds) if conds else None)
 
     @torch.no_grad()
-    def score(self, pairs, conditions="all", causal_source: bool = True, width=None, backend: str = "hip", dtype=torch.float32):
+    def score(self, pairs, conditions="all", causal_source: bool = True, width=None, backend: str = "hip", dtype=torch.float32,
+              dropout=None, pair0: int = 0):
         """Teacher-forced per-token NLL of every (sequence, pattern) pair — the forward and loss of 2.Pretrain_regenerator.py's
         train_epoch in eval mode.  conditions: "all" (each of the K one-hot condition weights, the memory slices stage 3 decodes
         with), "encoder" (softmax of the condition_encoder's logits: training's weights without the Gumbel noise, tau = 1) or a
         [n_w, n_pair, K] tensor used as is.  causal_source=False scores with the bidirectional source encoder of stage 3.
         width=(Ls, T) scores at those matrix widths (a slice of a file scores as inside the file).  `dtype` applies to
-        backend="torch" only."""
+        backend="torch" only.  dropout (a RegenDropout) scores in train mode: pair i takes the masks of global pair pair0 + i."""
         if backend not in ("hip", "torch"):
             raise ValueError(f"backend must be 'hip' or 'torch', not {backend!r}")
         src, src_len, tgt, tgt_len, Ls, T = self._pack_pairs(pairs, width)
         n = len(pairs)
+        pair0 = int(pair0)
         if isinstance(conditions, str):
             if conditions not in ("all", "encoder"):
                 raise ValueError(f"conditions must be 'all', 'encoder' or a [n_w, n_pair, K] tensor, not {conditions!r}")
@@ -769,17 +801,18 @@ class RegenModel:
             s_d, t_d, tl_d = src[a:b].to(dev).contiguous(), tgt[a:b].to(dev).contiguous(), tgt_len[a:b].to(dev).contiguous()
             wc = None if w is None else w[:, a:b]
             if hip:
-                c = self.condition_device(t_d, tl_d) if self.has_condition_encoder else None
+                c = self.condition_device(t_d, tl_d, None, dropout, pair0 + a) if self.has_condition_encoder else None
                 if wc is None:
                     wc = torch.softmax(c, -1)[None]
                 wc = wc.to(dev, torch.float32).contiguous()
-                x = self.score_device(s_d, src_len[a:b].to(dev).contiguous(), t_d, tl_d, wc, causal_source)
+                x = self.score_device(s_d, src_len[a:b].to(dev).contiguous(), t_d, tl_d, wc, causal_source, None, dropout, pair0 + a)
             else:
                 c = None
+                td = _TorchDrop.of(dropout, pair0 + a, b - a, dtype, dev)
                 if wc is None:
-                    _, c = self._score_torch(s_d, t_d, tl_d, None, True, causal_source, dtype)
+                    _, c = self._score_torch(s_d, t_d, tl_d, None, True, causal_source, dtype, None, td)
                     wc = torch.softmax(c, -1)[None]
-                x, c2 = self._score_torch(s_d, t_d, tl_d, wc, self.has_condition_encoder and c is None, causal_source, dtype)
+                x, c2 = self._score_torch(s_d, t_d, tl_d, wc, self.has_condition_encoder and c is None, causal_source, dtype, None, td)
                 c = c2 if c is None else c
             nll.append(x.cpu())
             if c is not None:
@@ -787,6 +820,44 @@ class RegenModel:
         n_w = 1 if w is None else w.shape[0]
         nll = torch.cat(nll, 1) if nll else torch.zeros(n_w, 0, T, dtype=odt)
         return ScoreResult(nll, (tgt[:, 1:] != 0).sum(1), torch.cat(cond) if cond else None, Ls, T)
+
+
+def _eval_mode(dropout):
+    """None and p = 0 are eval mode: the entry points without dropout, bit for bit"""
+    if dropout is not None and not isinstance(dropout, RegenDropout):
+        raise TypeError(f"dropout must be a RegenDropout or None, not {type(dropout).__name__}")
+    return dropout is None or dropout.p == 0.0
+
+
+def _drop_args(dropout, pair0):
+    if int(pair0) < 0:
+        raise ValueError("pair0 must not be negative")
+    return C.c_float(dropout.p), C.c_uint64(dropout.seed), C.c_uint32(dropout.step), C.c_int64(int(pair0))
+
+
+class _TorchDrop:
+    """the keep factors of one torch batch (global pairs pair0 .. pair0 + n - 1) as tensors, from the host mirror of the kernels'
+    masks (regen_dropout.py); a site is "src_emb", "tgt_emb" or (stack, layer, kind)"""
+
+    def __init__(self, dropout, pair0, n, dtype, device):
+        self.d, self.pairs, self.dtype, self.device, self.cache = dropout, range(pair0, pair0 + n), dtype, device, {}
+
+    @staticmethod
+    def of(dropout, pair0, n, dtype, device):
+        return None if _eval_mode(dropout) else _TorchDrop(dropout, pair0, n, dtype, device)
+
+    def _get(self, fn, s, shape):
+        sid = {"src_emb": regen_dropout.SITE_SRC_EMB, "tgt_emb": regen_dropout.SITE_TGT_EMB}[s] if isinstance(s, str) else regen_dropout.site(*s)
+        key = (sid, shape)
+        if key not in self.cache:
+            self.cache[key] = torch.from_numpy(fn(self.d, sid, list(self.pairs), *shape)).to(device=self.device, dtype=self.dtype)
+        return self.cache[key]
+
+    def rows(self, s, x):
+        return self._get(regen_dropout.keep_rows, s, tuple(x.shape[1:]))
+
+    def probs(self, s, a):
+        return self._get(regen_dropout.keep_probs, s, tuple(a.shape[2:]))
 
 
 class GradResult:

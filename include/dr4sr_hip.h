@@ -723,6 +723,37 @@ int dr4sr_regen_score_condition_bwd(const dr4sr_regen_plan* plan, const int64_t*
                                     const float* dlogits, void* workspace, int64_t workspace_bytes, float* grad, int32_t accumulate,
                                     void* stream);
 
+/* ---- additive to ABI 10: TRAIN MODE of the four teacher-forced calls (nn.Transformer's dropout, model.train() of
+ * 2.Pretrain_regenerator.py:270-292).  Each *_train form is its eval form plus (p, seed, step, pair0) in front of the stream: the keep
+ * factor 0 or 1 / (1 - p) at the reference's 30 sites, regenerated from (seed, step, site, element index) wherever it is consumed
+ * (csrc/common.h's 16-bit Philox decisions; p = 0.5 is exact), never stored.  Row i of a call takes the masks of GLOBAL pair pair0 + i, so
+ * a chunked run equals the unchunked one; the n_w weight vectors of a pair share their masks; the condition encoder's and the decoder's
+ * calls of one (seed, step) share the tgt_emb mask, as the reference drops tgt_emb once.  p == 0 dispatches to the eval kernels (the
+ * same bits as the eval entry point); p outside [0, 1) or pair0 outside [0, 2^40) is DR4SR_E_ARG.  Workspaces: the eval queries.
+ * Sites (what the mask hook of include/dr4sr_hip_hooks.h takes as `site`): DR4SR_REGEN_SITE(stack, layer, kind) with stack 0 source encoder,
+ * 1 condition encoder, 2 decoder; an encoder layer's kinds are 0 attention probabilities, 1 attention output, 2 FFN hidden, 3 FFN output, a
+ * decoder layer's 0 self probabilities, 1 self output, 2 cross probabilities, 3 cross output, 4 FFN hidden, 5 FFN output.  Element index
+ * (64-bit): hidden sites (pair 64 + position) 64 + column; FFN hidden (pair 64 + position) 256 + column; probabilities
+ * ((pair 2 + head) 64 + query position) 64 + key position.  DESIGN.md has the table; dr4sr_amd/regen_dropout.py is the host mirror. */
+#define DR4SR_REGEN_SITE_BASE 0x52470000u
+#define DR4SR_REGEN_SITE(stack, layer, kind) (DR4SR_REGEN_SITE_BASE + (stack) * 32 + (layer) * 8 + (kind))
+#define DR4SR_REGEN_SITE_SRC_EMB (DR4SR_REGEN_SITE_BASE + 96)
+#define DR4SR_REGEN_SITE_TGT_EMB (DR4SR_REGEN_SITE_BASE + 97)
+int dr4sr_regen_score_train(const dr4sr_regen_plan* plan, const int64_t* src, const int64_t* src_len, const int64_t* tgt,
+                            const int64_t* tgt_len, int64_t n_pair, int32_t Ls, int32_t T, const float* w, int32_t n_w,
+                            int32_t causal_source, void* workspace, int64_t workspace_bytes, float* nll, float p, uint64_t seed,
+                            uint32_t step, int64_t pair0, void* stream);
+int dr4sr_regen_score_condition_train(const dr4sr_regen_plan* plan, const int64_t* tgt, const int64_t* tgt_len, int64_t n_pair, int32_t T,
+                                      void* workspace, int64_t workspace_bytes, float* cond_logits, float p, uint64_t seed, uint32_t step,
+                                      int64_t pair0, void* stream);
+int dr4sr_regen_score_bwd_train(const dr4sr_regen_plan* plan, const int64_t* src, const int64_t* src_len, const int64_t* tgt,
+                                const int64_t* tgt_len, int64_t n_pair, int32_t Ls, int32_t T, const float* w, int32_t n_w,
+                                int32_t causal_source, const float* dnll, void* workspace, int64_t workspace_bytes, float* grad, float* dw,
+                                float* nll_or_null, int32_t accumulate, float p, uint64_t seed, uint32_t step, int64_t pair0, void* stream);
+int dr4sr_regen_score_condition_bwd_train(const dr4sr_regen_plan* plan, const int64_t* tgt, const int64_t* tgt_len, int64_t n_pair, int32_t T,
+                                          const float* dlogits, void* workspace, int64_t workspace_bytes, float* grad, int32_t accumulate,
+                                          float p, uint64_t seed, uint32_t step, int64_t pair0, void* stream);
+
 /* Test / measurement hooks (dr4sr_dropout_mask, dr4sr_*_launch_kernel) are NOT part of this product surface: they are declared in
  * include/dr4sr_hip_hooks.h, and nothing under dr4sr_amd/ calls them. */
 

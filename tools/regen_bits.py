@@ -10,7 +10,10 @@ Cases: the committed scoring / gradient fixture (tests/golden/regen_score_toys.n
 random toys-shaped pairs with K = 5 (the sizes of tests/test_gpu_regen_grad.py; the pair generator is the tests', restated here), and
 1 000 with K = 3.  Per case: nll with a causal and a bidirectional source for [2, n, K] weights and for the encoder's own (n_w = 2 and
 1), the condition logits, every gradient tensor, dw and the loss of loss_and_grad with [2, n, K] weights and with "encoder" + noise,
-and the condition encoder's gradients (condition_grad).
+and the condition encoder's gradients (condition_grad).  These are the 42 eval-mode arrays.
+A library that has the train-mode entry points adds `train:` arrays (dropout 0.5, seed 1, step 1, on the first 1 000 pairs of a case):
+both NLLs, the condition logits, both gradients with dw and loss, and condition_grad.  --compare --allow-new lists the arrays only the
+second file has as `new` instead of counting them as missing (an older build against a newer one).
 """
 import argparse
 import json
@@ -59,6 +62,23 @@ def outputs_of(torch, m, pairs, grad_pairs, width, seed, tag, out):
             out[f"{tag}:loss:{side}:{name}"] = np.float64(float(r.loss))
     cg = m.condition_grad(pairs, dl, width, "hip")
     out[f"{tag}:condition_grad"] = torch.cat([cg[k].reshape(-1) for k in cg]).cpu().numpy()
+    if hasattr(m, "score_bwd_device") and "dropout" in m.score_bwd_device.__code__.co_varnames:
+        from dr4sr_amd.regen import RegenDropout
+        d = RegenDropout(0.5, 1, 1)
+        tp, tg = pairs[:1000], grad_pairs[:1000]
+        r = m.score(tp, mixed[:, :len(tp)], True, width, "hip", dropout=d)
+        out[f"train:{tag}:nll:causal:n_w2"] = r.nll.numpy()
+        r = m.score(tp, "encoder", False, width, "hip", dropout=d)
+        out[f"train:{tag}:nll:bidir:encoder"] = r.nll.numpy()
+        out[f"train:{tag}:cond_logits"] = r.cond_logits.numpy()
+        for name, cond, causal, kw in (("causal:n_w2", mixed[:, :len(tg)], True, {}),
+                                       ("bidir:encoder", "encoder", False, dict(noise=noise[:len(tg)], tau=0.7, entropy_weight=1.0))):
+            r = m.loss_and_grad(tg, cond, causal, width, "hip", dropout=d, **kw)
+            out[f"train:{tag}:grad:{name}"] = torch.cat([r.grads[k].reshape(-1) for k in score_param_names()]).cpu().numpy()
+            out[f"train:{tag}:dw:{name}"] = r.dw.cpu().numpy()
+            out[f"train:{tag}:loss:{name}"] = np.float64(float(r.loss))
+        cg = m.condition_grad(tp, dl[:len(tp)], width, "hip", dropout=d)
+        out[f"train:{tag}:condition_grad"] = torch.cat([cg[k].reshape(-1) for k in cg]).cpu().numpy()
     print(f"{tag}: {len(pairs)} pairs, K = {m.K}: done", flush=True)
 
 
@@ -83,12 +103,15 @@ def run(path):
     print(f"{len(out) - 1} arrays from {out['library']} -> {path}")
 
 
-def compare(a_path, b_path):
+def compare(a_path, b_path, allow_new=False):
     a, b = np.load(a_path), np.load(b_path)
     print(f"A: {a['library']}\nB: {b['library']}")
     keys = sorted((set(a.files) | set(b.files)) - {"library"})
     bad = 0
     for k in keys:
+        if allow_new and k not in a.files:
+            print(f"new       {k}")
+            continue
         if k not in a.files or k not in b.files:
             print(f"MISSING   {k}")
             bad += 1
@@ -98,7 +121,8 @@ def compare(a_path, b_path):
         bad += not same
         note = "" if same else f"  differing entries: {int((x != y).sum()) if x.shape == y.shape else 'shape'}"
         print(f"{'equal    ' if same else 'DIFFERENT'} {k}  {x.dtype}{list(x.shape)}  finite {int(np.isfinite(x).sum())}/{x.size}{note}")
-    print(f"{len(keys) - bad} of {len(keys)} arrays bitwise equal")
+    common = [k for k in keys if k in a.files and k in b.files]
+    print(f"{len(common) - bad} of {len(common)} arrays of both files bitwise equal" if allow_new else f"{len(keys) - bad} of {len(keys)} arrays bitwise equal")
     return 1 if bad else 0
 
 
@@ -106,9 +130,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--compare", nargs=2, metavar=("A", "B"))
+    ap.add_argument("--allow-new", action="store_true", help="--compare: arrays only B has are listed as new, not as missing")
     a = ap.parse_args()
     if a.compare:
-        sys.exit(compare(*a.compare))
+        sys.exit(compare(*a.compare, allow_new=a.allow_new))
     if not a.out:
         ap.error("--out or --compare")
     run(a.out)

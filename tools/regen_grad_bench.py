@@ -11,6 +11,9 @@ reference's batch) and 4 096 pairs, with explicit [2, n, 5] weights and with "en
                 per-pair membership check, copies, every chunk, synchronised): median of 3 after one warm-up
   torch_ms      fp32 autograd through the eager restatement on the same GPU over the same rows (forward + backward of the same scalar)
 One JSON line per case on stdout and in --out.  --profile runs only the HIP path (for rocprofv3 --kernel-trace --stats).
+--dropout P measures TRAIN MODE instead: the HIP calls take RegenDropout(P, seed 1, step 1) with pair0 = the chunk's first pair (the
+DropPhilox kernels), and torch_ms is the same autograd with torch's own random masks of the same shapes at the same 30 sites (what
+model.train() costs in torch; not the host mirror's masks, whose numpy generation is no part of a training step).
 """
 import argparse
 import json
@@ -31,6 +34,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--dropout", type=float, default=0.0, help="train mode with this drop probability (0: eval mode)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -41,6 +45,14 @@ def main():
     m = regen.RegenModel.from_state_dict(regen.random_state_dict(seed=3, std=0.3, condition_encoder=True), dev)
     all_pairs = toys_pairs(1200)
     lib = regen._lib.load()
+    drop = regen.RegenDropout(a.dropout, 1, 1) if a.dropout > 0 else None
+
+    class TorchRandomDrop:                  # torch's own masks at the restatement's sites
+        def rows(self, s, x):
+            return (torch.rand_like(x) >= a.dropout).to(x.dtype) / (1.0 - a.dropout)
+        probs = rows
+
+    tdrop = TorchRandomDrop() if drop is not None else None
     step = regen.SCORE_BWD_PAIRS_PER_CALL
     lines = []
     for n in a.sizes:
@@ -69,18 +81,18 @@ def main():
             def run_hip():
                 for i, (s, sl, t, tl, lo) in enumerate(chunks):
                     hi = lo + s.shape[0]
-                    c = m.condition_device(t, tl, wsc).requires_grad_(True) if mode == "encoder" else None
+                    c = m.condition_device(t, tl, wsc, drop, lo).requires_grad_(True) if mode == "encoder" else None
                     w, w0, ent = weights_of(c, lo, hi)
                     dnll = torch.full((n_w, hi - lo, T), 1.0 / n_tok, device=dev)
-                    _, dw, _ = m.score_bwd_device(s, sl, t, tl, w, dnll, True, grad, i > 0, ws)
+                    _, dw, _ = m.score_bwd_device(s, sl, t, tl, w, dnll, True, grad, i > 0, ws, drop, lo)
                     if mode == "encoder":
                         (dl,) = torch.autograd.grad((w0 * dw[0]).sum() + ent, c)
-                        m.condition_bwd_device(t, tl, dl.contiguous(), grad, True, wsc)
+                        m.condition_bwd_device(t, tl, dl.contiguous(), grad, True, wsc, drop, lo)
 
             def run_fwd():
                 for s, sl, t, tl, lo in chunks:
-                    c = m.condition_device(t, tl, wsc) if mode == "encoder" else None
-                    m.score_device(s, sl, t, tl, weights_of(c, lo, lo + s.shape[0])[0], True, ws)
+                    c = m.condition_device(t, tl, wsc, drop, lo) if mode == "encoder" else None
+                    m.score_device(s, sl, t, tl, weights_of(c, lo, lo + s.shape[0])[0], True, ws, drop, lo)
 
             if a.profile:
                 run_hip()
@@ -95,15 +107,15 @@ def main():
                 for lo in range(0, n, regen.ROWS_PER_TORCH):
                     s, t, tl = (x[lo:lo + regen.ROWS_PER_TORCH].to(dev) for x in (src, tgt, tgt_len))
                     hi = lo + s.shape[0]
-                    c = m._score_torch(s, t, tl, None, True, True, torch.float32, leaves)[1] if mode == "encoder" else None
+                    c = m._score_torch(s, t, tl, None, True, True, torch.float32, leaves, tdrop)[1] if mode == "encoder" else None
                     w, w0, ent = weights_of(c, lo, hi)
                     if mode == "encoder":
                         w = w0[None]
-                    nll, _ = m._score_torch(s, t, tl, w, False, True, torch.float32, leaves)
+                    nll, _ = m._score_torch(s, t, tl, w, False, True, torch.float32, leaves, tdrop)
                     (nll.sum() / n_tok + (ent if ent is not None else 0.0)).backward()
 
             r = {"metric": "regen_loss_and_grad", "mode": mode, "pairs": n, "n_w": n_w, "live_tokens": n_tok * n_w, "K": m.K, "width": [Ls, T],
-                 "pairs_per_call": step, "workspace_mb": round(ws.numel() / 2 ** 20, 1), "repeats": a.repeats}
+                 "pairs_per_call": step, "dropout": a.dropout, "workspace_mb": round(ws.numel() / 2 ** 20, 1), "repeats": a.repeats}
             for key, fn in (("fwd_ms", run_fwd), ("hip_ms", run_hip), ("torch_ms", run_torch)):
                 med, lo_, hi_ = median_ms(torch, fn, a.warmup, a.repeats)
                 r.update({key: round(med, 3), key + "_min": round(lo_, 3), key + "_max": round(hi_, 3)})
@@ -115,7 +127,7 @@ def main():
             for _ in range(1 + 3):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                m.loss_and_grad(pairs, cond, True, None, "hip", **call)
+                m.loss_and_grad(pairs, cond, True, None, "hip", dropout=drop, **call)
                 torch.cuda.synchronize()
                 wall.append((time.perf_counter() - t0) * 1e3)
             r["loss_and_grad_wall_ms"] = round(float(np.median(wall[1:])), 3)
