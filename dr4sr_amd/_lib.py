@@ -319,6 +319,11 @@ SYMBOLS = {
                                               C.c_int64, C.c_void_p]),
     "dr4sr_regen_score_condition_bwd_train": (C.c_int, [_RPLANP, _i64p, _i64p, C.c_int64, C.c_int32, _f32p, C.c_void_p, C.c_int64, _f32p,
                                                         C.c_int32, C.c_float, C.c_uint64, C.c_uint32, C.c_int64, C.c_void_p]),
+    # additive to ABI 10: the condition head of the pre-training step (csrc/regen_head.hip)
+    "dr4sr_regen_head_fwd": (C.c_int, [_f32p, _f32p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int64, C.c_uint64, C.c_uint32, C.c_int64,
+                                       _f32p, _f32p, _f32p, _f32p, C.c_void_p]),
+    "dr4sr_regen_head_bwd": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int64, C.c_int64,
+                                       _f32p, _f32p, _f32p, C.c_int64, C.c_void_p]),
     "dr4sr_crash_line_set": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32]),           # measurement hook (include/dr4sr_hip_hooks.h)
 }
 

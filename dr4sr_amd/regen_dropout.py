@@ -20,6 +20,8 @@ import numpy as np
 SITE_BASE = 0x52470000
 SITE_SRC_EMB = SITE_BASE + 96
 SITE_TGT_EMB = SITE_BASE + 97
+SITE_GUMBEL = SITE_BASE + 98      # the condition head's Gumbel noise (csrc/regen_head.hip): 32-bit words, four elements per call
+GUMBEL_STRIDE = 8                 # elements per pair in the noise stream's index, whatever K <= 8 is
 STACK_SRC, STACK_COND, STACK_DEC = 0, 1, 2
 ROWS = 64            # positions per pair in every index (the position table has 50 rows)
 N_SITES = 30
@@ -117,3 +119,33 @@ def keep_probs(d: RegenDropout, site_id: int, pairs, n_q: int, n_k: int):
     call = (row[..., None] * np.uint64(ROWS) + np.arange(0, ROWS, 8, dtype=np.uint64)) >> np.uint64(3)
     keep = _keep8(d, site_id, call).reshape(len(pairs), 2, n_q, ROWS)[..., :n_k]
     return np.where(keep, d.scale(), np.float32(0.0)).astype(np.float32)
+
+
+def gumbel_u(words):
+    """fp32 uniforms of 32-bit Philox words, bit for bit the device's (csrc/regen_head.hip gumbel_of): ((r >> 8) + 0.5) * 2^-24 with
+    the sum and the product rounded to fp32.  Above 2^23 the + 0.5 is a tie that rounds to even, and the largest 24-bit value would
+    round up to u = 1, where -log(-log(u)) is infinite: u is held at the largest fp32 below 1, so it lies strictly inside (0, 1)"""
+    r = np.asarray(words, dtype=np.uint64) & _M32
+    u = ((r >> np.uint64(8)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -24)
+    return np.minimum(u, np.nextafter(np.float32(1.0), np.float32(0.0))).astype(np.float32)
+
+
+def gumbel_words(seed: int, step: int, pairs, K: int):
+    """uint64 [n, K]: the Philox words of the noise elements (pair, k) of GLOBAL pair indices: element e = pair * 8 + k is word e & 3
+    of call e >> 2 of the SITE_GUMBEL stream of (seed, step)"""
+    if not (1 <= int(K) <= GUMBEL_STRIDE):
+        raise ValueError(f"K must be in 1..{GUMBEL_STRIDE}, not {K!r}")
+    pairs = np.asarray(pairs, dtype=np.uint64).reshape(-1)
+    e = pairs[:, None] * np.uint64(GUMBEL_STRIDE) + np.arange(int(K), dtype=np.uint64)[None, :]
+    call = e >> np.uint64(2)
+    w = np.stack(philox4x32_10(call & _M32, call >> np.uint64(32), np.uint64(SITE_GUMBEL), np.uint64(int(step) & 0xFFFFFFFF),
+                               int(seed) & 0xFFFFFFFFFFFFFFFF), -1)
+    return np.take_along_axis(w, (e & np.uint64(3)).astype(np.int64)[..., None], -1)[..., 0]
+
+
+def gumbel_noise(seed: int, step: int, pairs, K: int):
+    """float32 [n, K]: the Gumbel(0, 1) noise the condition head generates for the given GLOBAL pair indices at (seed, step).  u is
+    the device's bit for bit; the two logs run in float64 here and the result is rounded to fp32 (the device's double logs may leave
+    the last fp32 bit different)"""
+    u = gumbel_u(gumbel_words(seed, step, pairs, K)).astype(np.float64)
+    return (-np.log(-np.log(u))).astype(np.float32)

@@ -754,6 +754,30 @@ int dr4sr_regen_score_condition_bwd_train(const dr4sr_regen_plan* plan, const in
                                           const float* dlogits, void* workspace, int64_t workspace_bytes, float* grad, int32_t accumulate,
                                           float p, uint64_t seed, uint32_t step, int64_t pair0, void* stream);
 
+/* ---- additive to ABI 10: the condition head of the pre-training step (csrc/regen_head.hip; 2.Pretrain_regenerator.py:270-292): what lies
+ * between dr4sr_regen_score_condition's logits and dr4sr_regen_score_bwd's weights, and back.  Plain fp32, one thread per pair, no
+ * atomics, only enqueues on `stream`; a pair's values depend on its GLOBAL index pair0 + i alone (a chunked batch gives the bits of the
+ * whole).  DR4SR_E_ARG: a null pointer, n_pair outside [1, 2^24), K outside [1, 8], T outside [1, 50], tau <= 0, n_tok < 1,
+ * n_batch < n_pair, pair0 outside [0, 2^40), slot < 0.
+ * forward: w [n_pair, K] = softmax((cond_logits + g) / tau), ent [n_pair] = -(w log(w + 1e-12)).sum(-1), dnll [1, n_pair, T] = 1 / n_tok
+ * (n_tok: the live target tokens of the whole BATCH, known to the host from the lengths).  g = noise [n_pair, K] when given (recorded
+ * samples), else Gumbel(0, 1) from the project's Philox convention: element e = (pair0 + i) * 8 + k is word e & 3 of the call with counter
+ * (e >> 2 low, e >> 2 high, DR4SR_REGEN_SITE_GUMBEL, step) under the key `seed`; u = ((r >> 8) + 0.5) 2^-24 in fp32, held below 1 (the
+ * largest 24-bit value rounds up to 1 in fp32), g = -log(-log(u)) with both logs in double, rounded to fp32.  noise_out, when given,
+ * receives the g that were used [n_pair, K].  dr4sr_amd/regen_dropout.py gumbel_noise is the host mirror.
+ * backward: dw [1, n_pair, K] (the gradient of the cross entropy with respect to w, as dr4sr_regen_score_bwd returns it for the dnll
+ * above), the forward's w and ent -> dlogits [n_pair, K], the gradient of CE + entropy_weight * (sum of ent over the batch / n_batch):
+ * (diag(w) - w w^T) / tau applied to dw + (entropy_weight / n_batch) (-log(w + 1e-12) - w / (w + 1e-12)).  The same launch adds the
+ * call's share of the step's log: loss_log[slot] += sum(nll [1, n_pair, T]) / n_tok and ent_log[slot] += sum(ent) / n_batch, each summed
+ * in a fixed order by one wave (either log may be NULL; nll only then).  The caller zeroes the slot once per step. */
+#define DR4SR_REGEN_SITE_GUMBEL (DR4SR_REGEN_SITE_BASE + 98)
+int dr4sr_regen_head_fwd(const float* cond_logits, const float* noise_or_null, int64_t n_pair, int32_t K, int32_t T, float tau,
+                         int64_t n_tok, uint64_t seed, uint32_t step, int64_t pair0, float* w, float* ent, float* dnll,
+                         float* noise_out_or_null, void* stream);
+int dr4sr_regen_head_bwd(const float* dw, const float* w, const float* ent, const float* nll, int64_t n_pair, int32_t K, int32_t T,
+                         float tau, float entropy_weight, int64_t n_batch, int64_t n_tok, float* dlogits, float* loss_log_or_null,
+                         float* ent_log_or_null, int64_t slot, void* stream);
+
 /* Test / measurement hooks (dr4sr_dropout_mask, dr4sr_*_launch_kernel) are NOT part of this product surface: they are declared in
  * include/dr4sr_hip_hooks.h, and nothing under dr4sr_amd/ calls them. */
 
