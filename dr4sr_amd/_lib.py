@@ -324,6 +324,11 @@ SYMBOLS = {
                                        _f32p, _f32p, _f32p, _f32p, C.c_void_p]),
     "dr4sr_regen_head_bwd": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int64, C.c_int64,
                                        _f32p, _f32p, _f32p, C.c_int64, C.c_void_p]),
+    # additive to ABI 10: graph propagation of the item table for the GNN model (csrc/gnn.hip)
+    "dr4sr_gnn_split_rows": (C.c_int32, []),
+    "dr4sr_gnn_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
+    "dr4sr_gnn_propagate": (C.c_int, [_i64p, C.c_void_p, _f32p, C.c_int32, C.c_int32, C.c_int32, _f32p, _f32p, C.c_int32, C.c_void_p, C.c_int64,
+                                      C.c_void_p]),
     "dr4sr_crash_line_set": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32]),           # measurement hook (include/dr4sr_hip_hooks.h)
 }
 

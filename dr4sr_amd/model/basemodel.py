@@ -150,13 +150,13 @@ class BaseModel(nn.Module):
                 logging.getLogger("CDR").info("train.deterministic: on (process-wide switch DR4SR_DETERMINISTIC, read when an engine is built)")
             _lib.set_env("DR4SR_DETERMINISTIC", "1")
             # bit-identical fits are tested for every shipped model: SASRec, CL4SRec, FMLP, GRU4Rec and MetaModel around each of them (round 6;
-            # tools/det_fit_check.py, tests/test_gpu_deterministic.py) — the fused steps, the autograd-path backwards and the dense scorer all
+            # tools/det_fit_check.py, tests/test_gpu_deterministic.py) and GNN (tests/test_gpu_gnn.py) — the fused steps, the autograd-path backwards and the dense scorer all
             # sum in a fixed order in the mode.  A model class outside that list gets a warning, not a promise
             name = type(self).__name__
             inner = str(config["model"].get("sub_model", "")) if name == "MetaModel" else name
-            if inner not in ("SASRec", "CL4SRec", "FMLP", "GRU4Rec"):
-                logging.getLogger("CDR").warning("train.deterministic: bit-identical fits are tested for SASRec, CL4SRec, FMLP, GRU4Rec and MetaModel around them "
-                                                 f"(tests/test_gpu_deterministic.py); {name}{'(' + inner + ')' if name == 'MetaModel' else ''} is not in that list")
+            if inner not in ("SASRec", "CL4SRec", "FMLP", "GRU4Rec") and name != "GNN":
+                logging.getLogger("CDR").warning("train.deterministic: bit-identical fits are tested for SASRec, CL4SRec, FMLP, GRU4Rec, MetaModel around them "
+                                                 f"(tests/test_gpu_deterministic.py) and GNN (tests/test_gpu_gnn.py); {name}{'(' + inner + ')' if name == 'MetaModel' else ''} is not in that list")
         self._graphs = {}
 
     # ------------------------------------------------------------------------------------------ setup

@@ -778,6 +778,25 @@ int dr4sr_regen_head_bwd(const float* dw, const float* w, const float* ent, cons
                          float tau, float entropy_weight, int64_t n_batch, int64_t n_tok, float* dlogits, float* loss_log_or_null,
                          float* ent_log_or_null, int64_t slot, void* stream);
 
+/* ---- additive to ABI 10: graph propagation of the item table for the GNN target model (csrc/gnn.hip; the reference's model/gnn.py:43-50)
+ *   out (+)= (in + A in + A^2 in + ... + A^n_hop in) / (n_hop + 1)
+ * A [n_items, n_items] is CSR in fp32: row_ptr [n_items + 1] int64, col [nnz] int32 with every row's columns ascending, val [nnz].  in and
+ * out are [n_items, D] fp32, D = 64 or 128 (anything else: DR4SR_E_SHAPE), and must not be the same buffer; in is only read.  accumulate = 0
+ * overwrites out, 1 adds onto it.  n_hop = 0 copies (adds) bit-exactly and needs no workspace.  For a symmetric A (what
+ * dr4sr_amd/model/gnn.py build_graph builds and asserts) the call is its own adjoint: forward in = E, out = G, accumulate 0; backward
+ * in = dG, out = dE, accumulate 1.
+ * One gather launch per hop (plus one single-workgroup launch per call that derives the chunk list of the long rows from row_ptr on the
+ * device), all on `stream`, capturable; no float atomics and every sum in a fixed order: the same inputs give the same bits.  A row with
+ * more than dr4sr_gnn_split_rows() edges is cut into chunks of that many edges, summed by separate waves and added in chunk order.
+ * The workspace (dr4sr_gnn_workspace_bytes for the graph's nnz) holds the tables of A^k in, the running sum and the chunks' partial sums;
+ * nothing in it survives a call.  DR4SR_E_ARG: a null pointer, in == out, n_items < 1, nnz < 0, n_hop outside [0, 64], accumulate not
+ * 0 / 1; DR4SR_E_WS: a null or too small workspace with n_hop > 0.  NOT checked on the host: the contents of row_ptr / col (column ids are
+ * clamped to [0, n_items) on the device). */
+int32_t dr4sr_gnn_split_rows(void);
+int64_t dr4sr_gnn_workspace_bytes(int32_t n_items, int32_t D, int64_t nnz);
+int dr4sr_gnn_propagate(const int64_t* row_ptr, const int32_t* col, const float* val, int32_t n_items, int32_t D, int32_t n_hop,
+                        const float* in, float* out, int32_t accumulate, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Test / measurement hooks (dr4sr_dropout_mask, dr4sr_*_launch_kernel) are NOT part of this product surface: they are declared in
  * include/dr4sr_hip_hooks.h, and nothing under dr4sr_amd/ calls them. */
 
