@@ -226,10 +226,15 @@ SYMBOLS = {
     "dr4sr_fmlp_launch_kernel": (C.c_int, [_FPLANP, C.c_int32, C.c_int32, C.c_void_p]),
     "dr4sr_meta_param_count": (C.c_int64, [C.c_int32]),
     "dr4sr_meta_select_workspace_floats": (C.c_int64, [C.c_int64]),
+    "dr4sr_meta_select_workspace_floats_d": (C.c_int64, [C.c_int64, C.c_int32]),
     "dr4sr_meta_select_fwd": (C.c_int, [_f32p, _f32p, _f32p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_float, _i64p, _i64p, C.c_int64, C.c_int32,
                                         C.c_int32, C.c_void_p, C.c_void_p, _f32p, C.c_void_p]),
     "dr4sr_meta_select_bwd": (C.c_int, [_f32p, _f32p, _f32p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_float, _i64p, _i64p, C.c_int64, C.c_int32,
                                         C.c_int32, C.c_void_p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_void_p]),
+    "dr4sr_meta_select_fwd_d": (C.c_int, [_f32p, _f32p, _f32p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_float, _i64p, _i64p, C.c_int64, C.c_int32,
+                                          C.c_int32, C.c_void_p, C.c_void_p, _f32p, C.c_void_p]),
+    "dr4sr_meta_select_bwd_d": (C.c_int, [_f32p, _f32p, _f32p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_float, _i64p, _i64p, C.c_int64, C.c_int32,
+                                          C.c_int32, C.c_void_p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_void_p]),
     "dr4sr_fd_step_size": (C.c_int, [_f32p, _f32p, C.c_int64, C.c_float, _f32p, C.c_void_p]),
     "dr4sr_fd_step_size_scratch_floats": (C.c_int64, []),
     "dr4sr_fd_step_size_ws": (C.c_int, [_f32p, _f32p, C.c_int64, C.c_float, _f32p, _f32p, C.c_void_p]),

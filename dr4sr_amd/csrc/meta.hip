@@ -10,6 +10,8 @@
 #include "common.h"
 #include "kernels.h"
 
+extern __shared__ __attribute__((aligned(16))) float smem[];
+
 namespace {
 
 constexpr int MD = 64;                                   // embed_dim == hidden width of the meta module
@@ -22,13 +24,13 @@ struct SelArgs {
     const float* gumbel;       // [n, 2] or null (Philox: -log(-log(u)))
     const int64_t* user_id;    // [B] or null
     const int64_t* target;     // [n]
-    const uint64_t* gate_in;   // [n] frozen ReLU pattern or null
-    uint64_t* gate_out;        // [n] or null
+    const uint64_t* gate_in;   // [n][D/64] frozen ReLU pattern or null
+    uint64_t* gate_out;        // [n][D/64] or null
     float* weight;             // [n]           (fwd)
     const float* d_weight;     // [n]           (bwd) upstream dL/dweight
     const float* scale;        // device scalar multiplying d_weight, or null
     float* d_query;            // [n, D] accumulated (bwd), may be null
-    float* part;               // [gridDim.x, N_PHI] per-block partial d_phi (bwd)
+    float* part;               // [gridDim.x, n_phi(D)] per-block partial d_phi (bwd)
     int64_t n;
     int L;
     float inv_tau;
@@ -201,6 +203,204 @@ __global__ __launch_bounds__(256) void k_meta_reduce(const float* __restrict__ p
     if (w == 0 && i < N_PHI) d_phi[i] += (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
 }
 
+// ------------------------------------------------------------------------------------------------ D = 128
+// Same semantics at twice the width; the D = 64 kernels above are left as they are.  One wave per position, lane l = hidden units l
+// and l + 64 (gate word 0 / 1).  W1 sits in LDS ONCE, as w1p[d][j] with a row stride of D + 1 floats: lanes over j (the
+// pre-activation) and lanes over d (d_query) both walk distinct banks, so the second orientation of the D = 64 kernel is not needed
+// (66 KiB instead of 128).  That is past the static limit: dynamic LDS.
+// dW1 cannot stay per lane (256 accumulators): the positions of one block iteration (one per wave) leave dh and q in LDS and the
+// WHOLE workgroup accumulates their outer products, thread (wave w, lane l) owning rows {l, l + 64} x columns [32 w, 32 w + 32) —
+// 64 accumulators, no cross-wave reduction, and a fixed order over positions.
+constexpr int WD = 128;
+constexpr int WSTR = WD + 1;                              // padded row of w1p
+constexpr int N_PHI_W = WD * WD + WD + 2 * WD + 2;        // 16 770
+constexpr int WCOLS = WD / SEL_WAVES;                     // dW1 columns per wave
+constexpr size_t SELW_FWD_LDS = (size_t)(WD * WSTR + SEL_WAVES * WD) * sizeof(float);
+constexpr size_t SELW_BWD_LDS = (size_t)(WD * WSTR + 2 * SEL_WAVES * WD + SEL_WAVES) * sizeof(float);
+static_assert(SELW_BWD_LDS <= 160 * 1024 && (WD * WSTR) % 4 == 0, "LDS budget / float4 alignment of the staging rows");
+
+struct WideUnit {                                          // what lane l holds of the meta module: units l (a) and l + 64 (b)
+    float b1a, b1b, w20a, w20b, w21a, w21b, b20, b21;
+};
+__device__ __forceinline__ WideUnit wide_unit(const float* __restrict__ phi, int lane) {
+    const float* P = phi + WD * WD;
+    WideUnit U;
+    U.b1a = P[lane]; U.b1b = P[64 + lane];
+    U.w20a = P[WD + lane]; U.w20b = P[WD + 64 + lane];
+    U.w21a = P[2 * WD + lane]; U.w21b = P[2 * WD + 64 + lane];
+    U.b20 = P[3 * WD]; U.b21 = P[3 * WD + 1];
+    return U;
+}
+
+__device__ __forceinline__ void stage_w1_wide(const float* __restrict__ phi, float* __restrict__ w1p) {
+    for (int i = threadIdx.x; i < WD * WD; i += blockDim.x) {
+        const int j = i / WD, d = i % WD;
+        w1p[d * WSTR + j] = phi[i];
+    }
+}
+
+struct WideEval { float ha, hb, z; bool ona, onb; uint64_t g0, g1; };
+// THE pre-activation / logit routine of both kernels: the forward records the ReLU pattern, the backward recomputes it when gate_in is
+// null — same code, same bits.  qs = this wave's query row in LDS.
+__device__ __forceinline__ WideEval wide_eval(const SelArgs& A, const WideUnit& U, const float* __restrict__ w1p,
+                                              const float* __restrict__ qs, int64_t p, int lane) {
+    float a0 = U.b1a, a1 = 0.f, a2 = 0.f, a3 = 0.f, c0 = U.b1b, c1 = 0.f, c2 = 0.f, c3 = 0.f;
+#pragma unroll 8
+    for (int d = 0; d < WD; d += 4) {
+        const float q0 = qs[d], q1 = qs[d + 1], q2 = qs[d + 2], q3 = qs[d + 3];
+        a0 = fmaf(w1p[(d + 0) * WSTR + lane], q0, a0); c0 = fmaf(w1p[(d + 0) * WSTR + 64 + lane], q0, c0);
+        a1 = fmaf(w1p[(d + 1) * WSTR + lane], q1, a1); c1 = fmaf(w1p[(d + 1) * WSTR + 64 + lane], q1, c1);
+        a2 = fmaf(w1p[(d + 2) * WSTR + lane], q2, a2); c2 = fmaf(w1p[(d + 2) * WSTR + 64 + lane], q2, c2);
+        a3 = fmaf(w1p[(d + 3) * WSTR + lane], q3, a3); c3 = fmaf(w1p[(d + 3) * WSTR + 64 + lane], q3, c3);
+    }
+    const float prea = (a0 + a1) + (a2 + a3), preb = (c0 + c1) + (c2 + c3);
+    WideEval E;
+    E.g0 = A.gate_in ? A.gate_in[2 * p] : __ballot(prea > 0.f);
+    E.g1 = A.gate_in ? A.gate_in[2 * p + 1] : __ballot(preb > 0.f);
+    E.ona = (E.g0 >> lane) & 1; E.onb = (E.g1 >> lane) & 1;
+    E.ha = E.ona ? prea : 0.f; E.hb = E.onb ? preb : 0.f;
+    const float s0 = wave_sum(fmaf(U.w20b, E.hb, U.w20a * E.ha)) + U.b20, s1 = wave_sum(fmaf(U.w21b, E.hb, U.w21a * E.ha)) + U.b21;
+    const float2 g = gumbel_pair(A, p);
+    E.z = ((s0 + g.x) - (s1 + g.y)) * A.inv_tau;
+    return E;
+}
+
+__global__ __launch_bounds__(SEL_WAVES * 64) void k_meta_select_fwd_wide(SelArgs A) {
+    float* w1p = smem;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    float* qs = smem + WD * WSTR + w * WD;
+    stage_w1_wide(A.phi, w1p);
+    const WideUnit U = wide_unit(A.phi, lane);
+    __syncthreads();
+    for (int64_t p = (int64_t)blockIdx.x * SEL_WAVES + w; p < A.n; p += (int64_t)gridDim.x * SEL_WAVES) {
+        if (A.target[p] == 0) {
+            if (lane == 0) { A.weight[p] = 0.f; if (A.gate_out) { A.gate_out[2 * p] = 0; A.gate_out[2 * p + 1] = 0; } }
+            continue;
+        }
+        qs[lane] = A.q[p * WD + lane];
+        qs[64 + lane] = A.q[p * WD + 64 + lane];
+        __builtin_amdgcn_wave_barrier();
+        const WideEval E = wide_eval(A, U, w1p, qs, p, lane);
+        const bool forced = A.user_id && A.user_id[p / A.L] == 0;
+        if (lane == 0) {
+            A.weight[p] = forced ? 1.0f : 1.0f / (1.0f + expf(-E.z));
+            if (A.gate_out) { A.gate_out[2 * p] = E.g0; A.gate_out[2 * p + 1] = E.g1; }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+__global__ __launch_bounds__(SEL_WAVES * 64) void k_meta_select_bwd_wide(SelArgs A) {
+    float* w1p = smem;
+    float* qt = smem + WD * WSTR;                            // [SEL_WAVES][WD] queries of this iteration's positions
+    float* dht = qt + SEL_WAVES * WD;                        // [SEL_WAVES][WD] their dL/dh
+    float* act = dht + SEL_WAVES * WD;                       // [SEL_WAVES] 1 = the position carries a gradient
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    float* qs = qt + w * WD;
+    float* dhs = dht + w * WD;
+    stage_w1_wide(A.phi, w1p);
+    const WideUnit U = wide_unit(A.phi, lane);
+    const float sc = A.scale ? *A.scale : 1.0f;
+    float acc[2][WCOLS];
+#pragma unroll
+    for (int c = 0; c < WCOLS; ++c) { acc[0][c] = 0.f; acc[1][c] = 0.f; }
+    float db1a = 0.f, db1b = 0.f, dw20a = 0.f, dw20b = 0.f, dw21a = 0.f, dw21b = 0.f, db2 = 0.f;
+    __syncthreads();
+    // block-uniform trip count: the outer-product phase below is a workgroup step
+    for (int64_t base = (int64_t)blockIdx.x * SEL_WAVES; base < A.n; base += (int64_t)gridDim.x * SEL_WAVES) {
+        const int64_t p = base + w;
+        bool live = p < A.n && A.target[p] != 0 && !(A.user_id && A.user_id[p / A.L] == 0);   // forced weight: constant, no gradient
+        float up = 0.f;
+        if (live) { up = A.d_weight[p] * sc; live = up != 0.f; }
+        if (live) {                                          // wave-uniform
+            qs[lane] = A.q[p * WD + lane];
+            qs[64 + lane] = A.q[p * WD + 64 + lane];
+            __builtin_amdgcn_wave_barrier();
+            const WideEval E = wide_eval(A, U, w1p, qs, p, lane);
+            const float y = 1.0f / (1.0f + expf(-E.z));
+            const float dz = up * y * (1.0f - y) * A.inv_tau;           // d/d logit0 = +dz, d/d logit1 = -dz
+            const float dha = E.ona ? (U.w20a - U.w21a) * dz : 0.f, dhb = E.onb ? (U.w20b - U.w21b) * dz : 0.f;
+            dw20a = fmaf(dz, E.ha, dw20a); dw20b = fmaf(dz, E.hb, dw20b);
+            dw21a = fmaf(-dz, E.ha, dw21a); dw21b = fmaf(-dz, E.hb, dw21b);
+            db2 += dz;
+            db1a += dha; db1b += dhb;
+            dhs[lane] = dha;
+            dhs[64 + lane] = dhb;
+            if (A.d_query) {
+                __builtin_amdgcn_wave_barrier();
+                float a0 = 0.f, a1 = 0.f, c0 = 0.f, c1 = 0.f;         // d_query[d] = sum_j W1[j][d] dh[j], d = lane | 64 + lane
+#pragma unroll 8
+                for (int j = 0; j < WD; j += 2) {
+                    const float h0 = dhs[j], h1 = dhs[j + 1];
+                    a0 = fmaf(w1p[lane * WSTR + j], h0, a0); c0 = fmaf(w1p[(64 + lane) * WSTR + j], h0, c0);
+                    a1 = fmaf(w1p[lane * WSTR + j + 1], h1, a1); c1 = fmaf(w1p[(64 + lane) * WSTR + j + 1], h1, c1);
+                }
+                A.d_query[p * WD + lane] += a0 + a1;
+                A.d_query[p * WD + 64 + lane] += c0 + c1;
+            }
+        }
+        if (lane == 0) act[w] = live ? 1.0f : 0.f;
+        __syncthreads();
+        // dW1[j][d] += dh[j] q[d] over this iteration's positions, in wave order
+        for (int s = 0; s < SEL_WAVES; ++s) {
+            if (act[s] == 0.f) continue;                     // block-uniform
+            const float ha = dht[s * WD + lane], hb = dht[s * WD + 64 + lane];
+            const float* qrow = qt + s * WD + w * WCOLS;
+#pragma unroll
+            for (int c = 0; c < WCOLS; c += 4) {
+                const float4 qv = ld4(qrow + c);
+                acc[0][c + 0] = fmaf(ha, qv.x, acc[0][c + 0]); acc[1][c + 0] = fmaf(hb, qv.x, acc[1][c + 0]);
+                acc[0][c + 1] = fmaf(ha, qv.y, acc[0][c + 1]); acc[1][c + 1] = fmaf(hb, qv.y, acc[1][c + 1]);
+                acc[0][c + 2] = fmaf(ha, qv.z, acc[0][c + 2]); acc[1][c + 2] = fmaf(hb, qv.z, acc[1][c + 2]);
+                acc[0][c + 3] = fmaf(ha, qv.w, acc[0][c + 3]); acc[1][c + 3] = fmaf(hb, qv.w, acc[1][c + 3]);
+            }
+        }
+        __syncthreads();                                     // qt / dht / act are rewritten by the next iteration
+    }
+    // one partial row per block: dW1 straight from its owners, the small vectors through a fixed-order cross-wave sum (LDS reused)
+    float* out = A.part + (size_t)blockIdx.x * N_PHI_W;
+#pragma unroll
+    for (int c = 0; c < WCOLS; ++c) {
+        out[lane * WD + w * WCOLS + c] = acc[0][c];
+        out[(64 + lane) * WD + w * WCOLS + c] = acc[1][c];
+    }
+    float* sm = w1p;                                         // b1[WD] | W2 row 0 [WD] | W2 row 1 [WD] | db2
+    for (int ww = 0; ww < SEL_WAVES; ++ww) {
+        if (w == ww) {
+            sm[lane] = ww == 0 ? db1a : sm[lane] + db1a;
+            sm[64 + lane] = ww == 0 ? db1b : sm[64 + lane] + db1b;
+            sm[WD + lane] = ww == 0 ? dw20a : sm[WD + lane] + dw20a;
+            sm[WD + 64 + lane] = ww == 0 ? dw20b : sm[WD + 64 + lane] + dw20b;
+            sm[2 * WD + lane] = ww == 0 ? dw21a : sm[2 * WD + lane] + dw21a;
+            sm[2 * WD + 64 + lane] = ww == 0 ? dw21b : sm[2 * WD + 64 + lane] + dw21b;
+            if (lane == 0) sm[3 * WD] = ww == 0 ? db2 : sm[3 * WD] + db2;      // every lane carries the same sum of dz
+        }
+        __syncthreads();
+    }
+    for (int i = threadIdx.x; i < 3 * WD; i += blockDim.x) out[WD * WD + i] = sm[i];
+    if (threadIdx.x == 0) {
+        out[WD * WD + 3 * WD] = sm[3 * WD];
+        out[WD * WD + 3 * WD + 1] = -sm[3 * WD];
+    }
+}
+
+// k_meta_reduce for a partial row of nphi floats.  A COPY (the D = 64 kernel is left as it is): the two must stay in step — the same split
+// of the partial rows over waves and the same summation tree, so that a width moved from one to the other keeps its bits.
+__global__ __launch_bounds__(256) void k_meta_reduce_wide(const float* __restrict__ part, int nblk, int nphi, float* __restrict__ d_phi) {
+    __shared__ float red[4][64];
+    const int c = threadIdx.x & 63, w = threadIdx.x >> 6, i = blockIdx.x * 64 + c;
+    float acc[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc[u] = 0.f;
+    if (i < nphi)
+        for (int b = w * 8; b < nblk; b += 32)
+#pragma unroll
+            for (int u = 0; u < 8; ++u) if (b + u < nblk) acc[u] += part[(size_t)(b + u) * nphi + i];
+    red[w][c] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+    __syncthreads();
+    if (w == 0 && i < nphi) d_phi[i] += (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+}
+
 // ------------------------------------------------------------------------------------------------ FD helpers
 __device__ __forceinline__ float block_sum(float v, float* sm) {
     v = wave_sum(v);
@@ -367,20 +567,37 @@ int sel_grid(int64_t n) {
 
 }  // namespace
 
-extern "C" int64_t dr4sr_meta_param_count(int32_t D) { return D == MD ? N_PHI : DR4SR_E_SHAPE; }
+extern "C" int64_t dr4sr_meta_param_count(int32_t D) { return D == MD ? N_PHI : D == WD ? N_PHI_W : DR4SR_E_SHAPE; }
 
 extern "C" int64_t dr4sr_meta_select_workspace_floats(int64_t n) { return (int64_t)sel_grid(n) * N_PHI; }
+
+extern "C" int64_t dr4sr_meta_select_workspace_floats_d(int64_t n, int32_t D) {
+    return D == MD ? (int64_t)sel_grid(n) * N_PHI : D == WD ? (int64_t)sel_grid(n) * N_PHI_W : DR4SR_E_SHAPE;
+}
 
 extern "C" int dr4sr_meta_select_fwd(const float* query, const float* phi, const float* gumbel, uint64_t seed, uint32_t step,
                                      const int32_t* step_dev, float tau, const int64_t* user_id, const int64_t* target, int64_t B, int32_t L, int32_t D,
                                      const uint64_t* gate_in, uint64_t* gate_out, float* weight, void* stream) {
     if (!query || !phi || !target || !weight || B < 0 || L <= 0 || !(tau > 0.f)) return DR4SR_E_ARG;
-    if (D != MD) return DR4SR_E_SHAPE;
+    if (D != MD) return DR4SR_E_SHAPE;                      // the D = 64 entry point, as ever; both widths: dr4sr_meta_select_fwd_d
+    return dr4sr_meta_select_fwd_d(query, phi, gumbel, seed, step, step_dev, tau, user_id, target, B, L, D, gate_in, gate_out, weight, stream);
+}
+
+extern "C" int dr4sr_meta_select_fwd_d(const float* query, const float* phi, const float* gumbel, uint64_t seed, uint32_t step,
+                                       const int32_t* step_dev, float tau, const int64_t* user_id, const int64_t* target, int64_t B, int32_t L, int32_t D,
+                                       const uint64_t* gate_in, uint64_t* gate_out, float* weight, void* stream) {
+    if (!query || !phi || !target || !weight || B < 0 || L <= 0 || !(tau > 0.f)) return DR4SR_E_ARG;
+    if (D != MD && D != WD) return DR4SR_E_SHAPE;
     const int64_t n = B * L;
     if (n == 0) return 0;
     SelArgs A{};
     A.q = query; A.phi = phi; A.gumbel = gumbel; A.user_id = user_id; A.target = target; A.gate_in = gate_in; A.gate_out = gate_out;
     A.weight = weight; A.n = n; A.L = L; A.inv_tau = 1.0f / tau; A.seed = seed; A.step = step; A.step_dev = step_dev;
+    if (D == WD) {
+        big_lds(k_meta_select_fwd_wide, SELW_FWD_LDS);
+        hipLaunchKernelGGL(k_meta_select_fwd_wide, dim3(sel_grid(n)), dim3(SEL_WAVES * 64), SELW_FWD_LDS, (hipStream_t)stream, A);
+        return (int)hipGetLastError();
+    }
     hipLaunchKernelGGL(k_meta_select_fwd, dim3(sel_grid(n)), dim3(SEL_WAVES * 64), 0, (hipStream_t)stream, A);
     return (int)hipGetLastError();
 }
@@ -391,6 +608,16 @@ extern "C" int dr4sr_meta_select_bwd(const float* query, const float* phi, const
                                      float* d_phi, float* workspace, void* stream) {
     if (!query || !phi || !target || !d_weight || !d_phi || !workspace || B < 0 || L <= 0 || !(tau > 0.f)) return DR4SR_E_ARG;
     if (D != MD) return DR4SR_E_SHAPE;
+    return dr4sr_meta_select_bwd_d(query, phi, gumbel, seed, step, step_dev, tau, user_id, target, B, L, D, gate_in, d_weight, scale, d_query,
+                                   d_phi, workspace, stream);
+}
+
+extern "C" int dr4sr_meta_select_bwd_d(const float* query, const float* phi, const float* gumbel, uint64_t seed, uint32_t step,
+                                       const int32_t* step_dev, float tau, const int64_t* user_id, const int64_t* target, int64_t B, int32_t L, int32_t D,
+                                       const uint64_t* gate_in, const float* d_weight, const float* scale, float* d_query,
+                                       float* d_phi, float* workspace, void* stream) {
+    if (!query || !phi || !target || !d_weight || !d_phi || !workspace || B < 0 || L <= 0 || !(tau > 0.f)) return DR4SR_E_ARG;
+    if (D != MD && D != WD) return DR4SR_E_SHAPE;
     const int64_t n = B * L;
     if (n == 0) return 0;
     SelArgs A{};
@@ -398,6 +625,12 @@ extern "C" int dr4sr_meta_select_bwd(const float* query, const float* phi, const
     A.d_weight = d_weight; A.scale = scale; A.d_query = d_query; A.part = workspace; A.n = n; A.L = L; A.inv_tau = 1.0f / tau;
     A.seed = seed; A.step = step; A.step_dev = step_dev;
     const int g = sel_grid(n);
+    if (D == WD) {
+        big_lds(k_meta_select_bwd_wide, SELW_BWD_LDS);
+        hipLaunchKernelGGL(k_meta_select_bwd_wide, dim3(g), dim3(SEL_WAVES * 64), SELW_BWD_LDS, (hipStream_t)stream, A);
+        hipLaunchKernelGGL(k_meta_reduce_wide, dim3((N_PHI_W + 63) / 64), dim3(256), 0, (hipStream_t)stream, workspace, g, N_PHI_W, d_phi);
+        return (int)hipGetLastError();
+    }
     hipLaunchKernelGGL(k_meta_select_bwd, dim3(g), dim3(SEL_WAVES * 64), 0, (hipStream_t)stream, A);
     hipLaunchKernelGGL(k_meta_reduce, dim3((N_PHI + 63) / 64), dim3(256), 0, (hipStream_t)stream, workspace, g, d_phi);
     return (int)hipGetLastError();

@@ -43,7 +43,7 @@ class _PhiStore:
     def __init__(self, lib, D: int, device):
         n = int(lib.dr4sr_meta_param_count(D))
         if n <= 0:
-            raise _lib.Dr4srError(f"MetaModel: embed_dim {D} unsupported by the meta-module kernels (D = 64)")
+            raise _lib.Dr4srError(f"MetaModel: embed_dim {D} unsupported by the meta-module kernels (D = 64 or 128)")
         self.n = n
         self.params = torch.zeros(n, dtype=torch.float32, device=device)
         self.grads = torch.zeros(n, dtype=torch.float32, device=device)
@@ -147,8 +147,8 @@ class MetaModel(BaseModel):
         self.meta_optimizer = self._get_meta_optimizers()
         self.metaloader_iter = iter(self.current_epoch_metaloaders(nepoch=0))
         n = self.engine.n_params
-        self._sel_ws = torch.empty(int(self.lib.dr4sr_meta_select_workspace_floats(
-            int(self.config["train"]["batch_size"]) * self.max_seq_len)), dtype=torch.float32, device=self.device)
+        self._sel_ws = torch.empty(int(self.lib.dr4sr_meta_select_workspace_floats_d(
+            int(self.config["train"]["batch_size"]) * self.max_seq_len, self.embed_dim)), dtype=torch.float32, device=self.device)
         self._stats = torch.zeros(2, dtype=torch.float32, device=self.device)
         self._e = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._fd_scratch = torch.zeros(int(self.lib.dr4sr_fd_step_size_scratch_floats()), dtype=torch.float32, device=self.device)
@@ -221,22 +221,22 @@ class MetaModel(BaseModel):
     def _select_fwd(self, q, user_id, target, gumbel, gate_in, gate_out):
         B, L = self._bl(target)
         w = torch.empty(B * L, dtype=torch.float32, device=q.device)
-        _lib.check(self.lib.dr4sr_meta_select_fwd(_lib.ptr(q), _lib.ptr(self._phi.params), _lib.ptr(gumbel), self.engine.seed,
+        _lib.check(self.lib.dr4sr_meta_select_fwd_d(_lib.ptr(q), _lib.ptr(self._phi.params), _lib.ptr(gumbel), self.engine.seed,
                                                   0, _lib.ptr(self._noise_step()), self._tau_eff(), _lib.ptr(user_id), _lib.ptr(target.contiguous()),
                                                   B, L, self.embed_dim, _lib.ptr(gate_in), _lib.ptr(gate_out), _lib.ptr(w),
-                                                  _lib.cur_stream()), "dr4sr_meta_select_fwd")
+                                                  _lib.cur_stream()), "dr4sr_meta_select_fwd_d")
         return w
 
     def _select_bwd(self, q, user_id, target, gumbel, gate_in, d_weight, d_query):
         B, L = self._bl(target)
-        need = int(self.lib.dr4sr_meta_select_workspace_floats(B * L))
+        need = int(self.lib.dr4sr_meta_select_workspace_floats_d(B * L, self.embed_dim))
         if self._sel_ws.numel() < need:
             self._sel_ws = torch.empty(need, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.dr4sr_meta_select_bwd(_lib.ptr(q), _lib.ptr(self._phi.params), _lib.ptr(gumbel), self.engine.seed,
+        _lib.check(self.lib.dr4sr_meta_select_bwd_d(_lib.ptr(q), _lib.ptr(self._phi.params), _lib.ptr(gumbel), self.engine.seed,
                                                   0, _lib.ptr(self._noise_step()), self._tau_eff(), _lib.ptr(user_id), _lib.ptr(target.contiguous()),
                                                   B, L, self.embed_dim, _lib.ptr(gate_in), _lib.ptr(d_weight), None,
                                                   _lib.ptr(d_query), _lib.ptr(self._phi.grads), _lib.ptr(self._sel_ws),
-                                                  _lib.cur_stream()), "dr4sr_meta_select_bwd")
+                                                  _lib.cur_stream()), "dr4sr_meta_select_bwd_d")
 
     def _noise_step(self):
         """device word keying the Gumbel noise: the sub-model engine's RNG step (bumped by every training forward), so that a
@@ -567,7 +567,7 @@ class MetaModel(BaseModel):
         # the train-batch graph: ONE set of dropout masks / Gumbel noise shared by every evaluation     utils.py:161-166
         rng0 = eng.state[_lib.STATE_RNGSTEP:_lib.STATE_RNGSTEP + 1].clone()
         self.counter += 1
-        gate = self._buf("gate", bt[self.fiid].numel(), torch.int64)
+        gate = self._buf("gate", bt[self.fiid].numel() * (self.embed_dim // 64), torch.int64)      # D/64 words per position
         q0 = sub._encode_raw(bt, True)
         self._select_fwd(q0, bt["user_id"].contiguous(), bt[self.fiid].contiguous(), self._gumbel, None, gate)
         rng_views = None

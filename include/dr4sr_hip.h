@@ -435,20 +435,35 @@ int dr4sr_gru4rec_encode_bwd(const dr4sr_gru4rec_plan* plan, int32_t training, i
  * DR4SR+ MetaModel (model/metamodel.py:19-197, utils/utils.py:134-252).
  *
  * The meta module is nn.Sequential(Linear(D,D), ReLU, Linear(D,2)) (metamodel.py:52-57); phi is its flat parameter vector
- * W1[D,D] | b1[D] | W2[2,D] | b2[2] (dr4sr_meta_param_count floats; D = 64).
+ * W1[D,D] | b1[D] | W2[2,D] | b2[2] (dr4sr_meta_param_count floats: 4 290 at D = 64, 16 770 at D = 128; any other D is
+ * DR4SR_E_SHAPE).  D = 128 goes through dr4sr_meta_select_fwd_d / _bwd_d (same arguments, same semantics).
  *
  * dr4sr_meta_select_fwd — MetaModel.selection + the two masks of training_step (metamodel.py:169-185):
  *   weight[p] = softmax((meta_module(query[p]) + gumbel[p]) / tau)[0];  1 where user_id[p / L] == 0;  0 where target[p] == 0.
  *   n = B*L positions (L = 1 for scalar-target models).  gumbel [n,2] explicit noise, or NULL: drawn in-kernel from Philox
  *   (seed, step) as -log(-log(u)) like F.gumbel_softmax; step_dev != NULL: the step is *step_dev (a device word such as the plan's
  *   state[RNGSTEP], so that a captured graph draws fresh noise on every replay).  tau = clip(tau, tau_min) is passed by the caller.
- *   gate_in  [n] (NULL = off): a FROZEN ReLU pattern (bit j = unit j active) used instead of (pre > 0);
- *   gate_out [n] (NULL = off): the pattern this call used.
+ *   gate_in  [n][D/64] (NULL = off): a FROZEN ReLU pattern used instead of (pre > 0) — D/64 uint64 words per position, position-major;
+ *            bit l of word h = hidden unit 64 h + l active (D = 64: one word per position);
+ *   gate_out [n][D/64] (NULL = off): the pattern this call used, same layout.
  * dr4sr_meta_select_bwd — backward of the above for upstream d_weight[n] (times *scale if scale != NULL):
  *   d_query [n,D] is ACCUMULATED (+=; NULL = skip), d_phi ACCUMULATED, deterministically (per-block partials in `workspace`,
- *   dr4sr_meta_select_workspace_floats(n) floats, summed in a fixed order). */
+ *   dr4sr_meta_select_workspace_floats_d(n, D) floats, summed in a fixed order: two calls on the same inputs are bitwise equal).
+ *   dr4sr_meta_select_workspace_floats(n) is the D = 64 size. */
 int64_t dr4sr_meta_param_count(int32_t D);
 int64_t dr4sr_meta_select_workspace_floats(int64_t n);
+int64_t dr4sr_meta_select_workspace_floats_d(int64_t n, int32_t D);
+/* D = 64 or 128 (dr4sr_meta_select_fwd / _bwd below keep meaning D = 64 alone and answer DR4SR_E_SHAPE to any other width, as they
+ * always have; at D = 64 the _d forms ARE those calls, bit for bit): */
+int dr4sr_meta_select_fwd_d(const float* query, const float* phi, const float* gumbel, uint64_t seed, uint32_t step,
+                            const int32_t* step_dev, float tau,
+                            const int64_t* user_id, const int64_t* target, int64_t B, int32_t L, int32_t D,
+                            const uint64_t* gate_in, uint64_t* gate_out, float* weight, void* stream);
+int dr4sr_meta_select_bwd_d(const float* query, const float* phi, const float* gumbel, uint64_t seed, uint32_t step,
+                            const int32_t* step_dev, float tau,
+                            const int64_t* user_id, const int64_t* target, int64_t B, int32_t L, int32_t D,
+                            const uint64_t* gate_in, const float* d_weight, const float* scale, float* d_query, float* d_phi,
+                            float* workspace, void* stream);
 int dr4sr_meta_select_fwd(const float* query, const float* phi, const float* gumbel, uint64_t seed, uint32_t step,
                           const int32_t* step_dev, float tau,
                           const int64_t* user_id, const int64_t* target, int64_t B, int32_t L, int32_t D,
