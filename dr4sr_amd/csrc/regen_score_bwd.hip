@@ -15,7 +15,10 @@
 // Activations: every tile kernel runs its forward again, through the same functions as the scoring kernels (regen_score_fwd.h) with
 // the KeepRec policy, which writes what a weight gradient needs into the tile's slot RECORDS in the workspace; the backward chain adds
 // every per-token output gradient (empty slots hold zero gradients and finite activations); the LDS holds one operation's
-// working set (the forward's layout + one score-gradient buffer).
+// working set (the forward's layout + one score-gradient buffer).  The chain of a layer is the forward's blocks in reverse, one text
+// for the three kernels as in regen_score_fwd.h: ffn_block_bwd, self_block_bwd (with self_attention_bwd or src_attention_bwd as its
+// attention) and the decoder's cross_block_bwd, so a kernel's backward layer loop is two or three calls under the two or three forward
+// calls it differentiates.  What differs between the kernels is an argument or is marked "KEPT DIFFERENCE".
 //   k_rsb_wgrad      every weight, bias and LayerNorm gradient as one job list: dW[n][k] = sum over records of dY[n] X[k] (a bias is the
 //                    job with X = 1).  The records are cut into NSPLIT contiguous ranges, each summed in record order into its own
 //                    partial slab.
@@ -117,10 +120,18 @@ __device__ __forceinline__ void drop_grad64(const DropPhilox& dp, uint32_t site,
 }
 
 // U[64][FLD] = U keep gelu'(hp) over the first `nrec` rows, into the record's dhp too: the gradient behind the FFN's hidden site
-template <class Rows>
-__device__ __forceinline__ void gelu_bwd64(const DropPhilox& dp, uint32_t site, const Rows& rows, float* U, float* rec, int tf, int f_hp, int f_dhp,
+// (eval mode: no factor, and an element per thread rather than the 8 of a Philox call)
+template <class Drop, class Rows>
+__device__ __forceinline__ void gelu_bwd64(const Drop& dp, uint32_t site, const Rows& rows, float* U, float* rec, int tf, int f_hp, int f_dhp,
                                            int nrec) {
-    {
+    if constexpr (!Drop::on) {
+        for (int e = threadIdx.x; e < nrec * RF; e += NT) {
+            const int s = e / RF, c = e % RF;
+            const float d = U[s * FLD + c] * gelu_grad_exact(rec[(size_t)s * tf + f_hp + c]);
+            U[s * FLD + c] = d;
+            rec[(size_t)s * tf + f_dhp + c] = d;
+        }
+    } else {
         for (int u = threadIdx.x; u < nrec * (RF / 8); u += NT) {
             const int s = u / (RF / 8), c0 = (u % (RF / 8)) * 8;
             int64_t pair = 0;
@@ -216,6 +227,94 @@ __device__ __forceinline__ void self_attention_bwd(const Drop& dp, uint32_t site
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------- layer blocks
+// The backward of the layer blocks of regen_score_fwd.h, with the same arguments: `lo` and the indices of the block's weights, the
+// site numbering of the forward block, X [64][XLD] the residual stream (in: the gradient of the block's output, out: of its input),
+// T and U scratch.  `rec, tf, nrec`: the first record, the record stride in floats and the number of records that exist.
+// KEPT DIFFERENCE: the tile kernels have nrec = 64 records, a source row has Ls, which bounds every record access and the GELU loop.
+// KEPT DIFFERENCE: G, a free [64][XLD] buffer for the gradient behind an output dropout site (train mode only), is the caller's: the
+// tile kernels have DS, idle between two attention blocks; the source kernel has no such buffer and lends T or S (see there).
+struct LnBwdRec { int v, g, y, dv; };              // a LayerNorm: its input; what ln_bwd64 leaves: dy * xhat, dy, the input's gradient
+struct FfnBwdRec { LnBwdRec n; int hp, dhp; };     // the FFN block: the hidden layer before GELU and its gradient
+struct SelfBwdRec { LnBwdRec n; int qkv, dqkv; };  // a self-attention block: q | k | v and their gradient
+struct CrossBwdRec { LnBwdRec n; int q, dq; };     // the cross-attention block: q and its gradient
+
+__device__ __forceinline__ void add64(float* X, const float* A) {
+    for (int e = threadIdx.x; e < TM * RD; e += NT) X[(e / RD) * XLD + e % RD] += A[(e / RD) * XLD + e % RD];
+}
+
+// X += A[64][KR] W through T: a linear's input gradient joins the residual stream.  Starts behind a barrier, ends behind one.
+template <int KR>
+__device__ __forceinline__ void add_dx(const float* A, int lda, const float* __restrict__ W, float* X, float* T) {
+    gemm_dx<KR, 1>(A, lda, W, T, XLD);
+    __syncthreads();
+    add64(X, T);
+    __syncthreads();
+}
+
+// the block's LayerNorm and output projection: T = (dL/d(LayerNorm input), dropped at `site` in train mode) Wo.  No barrier at the end.
+template <class Drop, class Rows>
+__device__ __forceinline__ void out_proj_bwd(const Drop& dp, uint32_t site, const Rows& rows, LnBwdRec f, const float* P, const int64_t* lo, int outw,
+                                             int nw, float eps, float* X, float* T, float* G, float* rec, int tf, int nrec) {
+    ln_bwd64(X, rec, f.v, P + lo[nw], eps, f.g, f.y, f.dv, tf, nrec);
+    __syncthreads();
+    if constexpr (Drop::on) {              // the dropped gradient is the linear's dY
+        drop_grad64(dp, site, rows, X, G, rec, tf, f.dv, nrec);
+        __syncthreads();
+        gemm_dx<RD, 1>(G, XLD, P + lo[outw], T, XLD);
+    } else {
+        gemm_dx<RD, 1>(X, XLD, P + lo[outw], T, XLD);
+    }
+}
+
+// FFN: sites site0 (hidden) and site0 + 1 (output), as ffn_block_fwd numbers them
+template <class Drop, class Rows>
+__device__ __forceinline__ void ffn_block_bwd(const Drop& dp, uint32_t site0, const Rows& rows, FfnBwdRec f, const float* P, const int64_t* lo, int w1,
+                                              int w2, int nw, float eps, float* X, float* T, float* U, float* G, float* rec, int tf, int nrec) {
+    ln_bwd64(X, rec, f.n.v, P + lo[nw], eps, f.n.g, f.n.y, f.n.dv, tf, nrec);
+    __syncthreads();
+    if constexpr (Drop::on) {
+        drop_grad64(dp, site0 + 1, rows, X, G, rec, tf, f.n.dv, nrec);
+        __syncthreads();
+        gemm_dx<RD, 4>(G, XLD, P + lo[w2], U, FLD);
+    } else {
+        gemm_dx<RD, 4>(X, XLD, P + lo[w2], U, FLD);
+    }
+    __syncthreads();
+    gelu_bwd64(dp, site0, rows, U, rec, tf, f.hp, f.dhp, nrec);
+    __syncthreads();
+    add_dx<RF>(U, FLD, P + lo[w1], X, T);
+}
+
+// self-attention: attend() turns q | k | v in U [64][QLD] and dO in T into the record's dQKV (site0: its probabilities; site0 + 1: the
+// block's output, as self_block_fwd numbers them)
+template <class Drop, class Rows, class Attend>
+__device__ __forceinline__ void self_block_bwd(const Drop& dp, uint32_t site0, const Rows& rows, SelfBwdRec f, const float* P, const int64_t* lo,
+                                               int inw, int outw, int nw, float eps, float* X, float* T, float* U, float* G, float* rec, int tf,
+                                               int nrec, Attend attend) {
+    out_proj_bwd(dp, site0 + 1, rows, f.n, P, lo, outw, nw, eps, X, T, G, rec, tf, nrec);
+    load64(U, QLD, rec, f.qkv, 3 * RD, tf, nrec);
+    __syncthreads();
+    attend();
+    __syncthreads();
+    load64(U, QLD, rec, f.dqkv, 3 * RD, tf, nrec);
+    __syncthreads();
+    add_dx<3 * RD>(U, QLD, P + lo[inw], X, T);
+}
+
+// the input rows of a tile kernel: both embedding terms went through the tgt_emb mask, so does their gradient; dead slots store zeros
+template <class Drop>
+__device__ __forceinline__ void tile_input_bwd(const Drop& dp, const TileRows& rows, float* X, float* rec, int tf, int f_dx0) {
+    if constexpr (Drop::on) {
+        drop_tile<RD>(dp, DR4SR_REGEN_SITE_TGT_EMB, X, XLD, rows);
+        __syncthreads();
+    }
+    for (int e = threadIdx.x; e < TM * RD; e += NT) {
+        const int s = e / RD, c = e % RD;
+        rec[(size_t)s * tf + f_dx0 + c] = rows.tb.tok_row[s] >= 0 ? X[s * XLD + c] : 0.f;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------- the tile
 template <class... D>      // D: nothing (eval mode) or DropPhilox
 __global__ __launch_bounds__(NT) void k_rsb_cond_tile(const float* __restrict__ P, ScoreOff off, float eps, int n_rows, int K,
@@ -286,59 +385,13 @@ __global__ __launch_bounds__(NT) void k_rsb_cond_tile(const float* __restrict__ 
     for (int l = RNL - 1; l >= 0; --l) {
         const int64_t* lo = off.o + T_CENC + 12 * l;
         const int f = l * LF;
-        ln_bwd64(X, rec, f + F_V2, P + lo[E_N2W], eps, f + F_G2, f + F_Y2, f + F_DV2);
-        __syncthreads();
-        if constexpr (Drop::on) {          // DS is free between two attention blocks: the dropped gradient is the linear's dY
-            drop_grad64(dp, rs_site(ST_COND, l, 3), rows, X, DS, rec, TOKF, f + F_DV2, TM);
-            __syncthreads();
-            gemm_dx<RD, 4>(DS, XLD, P + lo[E_W2], U, FLD);
-        } else {
-            gemm_dx<RD, 4>(X, XLD, P + lo[E_W2], U, FLD);
-        }
-        __syncthreads();
-        if constexpr (Drop::on) {
-            gelu_bwd64(dp, rs_site(ST_COND, l, 2), rows, U, rec, TOKF, f + F_HP, f + F_DHP, TM);
-        } else {
-            for (int e = threadIdx.x; e < TM * RF; e += NT) {
-                const int s = e / RF, c = e % RF;
-                const float d = U[s * FLD + c] * gelu_grad_exact(rec[(size_t)s * TOKF + f + F_HP + c]);
-                U[s * FLD + c] = d;
-                rec[(size_t)s * TOKF + f + F_DHP + c] = d;
-            }
-        }
-        __syncthreads();
-        gemm_dx<RF, 1>(U, FLD, P + lo[E_W1], Tt, XLD);
-        __syncthreads();
-        for (int e = threadIdx.x; e < TM * RD; e += NT) X[(e / RD) * XLD + e % RD] += Tt[(e / RD) * XLD + e % RD];
-        __syncthreads();
-        ln_bwd64(X, rec, f + F_V1, P + lo[E_N1W], eps, f + F_G1, f + F_Y1, f + F_DV1);
-        __syncthreads();
-        if constexpr (Drop::on) {
-            drop_grad64(dp, rs_site(ST_COND, l, 1), rows, X, DS, rec, TOKF, f + F_DV1, TM);
-            __syncthreads();
-            gemm_dx<RD, 1>(DS, XLD, P + lo[E_OUTW], Tt, XLD);
-        } else {
-            gemm_dx<RD, 1>(X, XLD, P + lo[E_OUTW], Tt, XLD);
-        }
-        load64(U, QLD, rec, f + F_QKV, 3 * RD);
-        __syncthreads();
-        self_attention_bwd(dp, rs_site(ST_COND, l, 0), tb, U, Tt, PS, DS, rec + f + F_DQKV, scale);
-        __syncthreads();
-        load64(U, QLD, rec, f + F_DQKV, 3 * RD);
-        __syncthreads();
-        gemm_dx<3 * RD, 1>(U, QLD, P + lo[E_INW], Tt, XLD);
-        __syncthreads();
-        for (int e = threadIdx.x; e < TM * RD; e += NT) X[(e / RD) * XLD + e % RD] += Tt[(e / RD) * XLD + e % RD];
-        __syncthreads();
+        ffn_block_bwd(dp, rs_site(ST_COND, l, 2), rows, {{f + F_V2, f + F_G2, f + F_Y2, f + F_DV2}, f + F_HP, f + F_DHP}, P, lo, E_W1, E_W2, E_N2W,
+                      eps, X, Tt, U, DS, rec, TOKF, TM);
+        self_block_bwd(dp, rs_site(ST_COND, l, 0), rows, {{f + F_V1, f + F_G1, f + F_Y1, f + F_DV1}, f + F_QKV, f + F_DQKV}, P, lo, E_INW, E_OUTW,
+                       E_N1W, eps, X, Tt, U, DS, rec, TOKF, TM,
+                       [&] { self_attention_bwd(dp, rs_site(ST_COND, l, 0), tb, U, Tt, PS, DS, rec + f + F_DQKV, scale); });
     }
-    if constexpr (Drop::on) {              // both embedding terms went through the tgt_emb mask: so does their gradient
-        drop_tile<RD>(dp, DR4SR_REGEN_SITE_TGT_EMB, X, XLD, rows);
-        __syncthreads();
-    }
-    for (int e = threadIdx.x; e < TM * RD; e += NT) {
-        const int s = e / RD, c = e % RD;
-        rec[(size_t)s * TOKF + F_DX0 + c] = tb.tok_row[s] >= 0 ? X[s * XLD + c] : 0.f;
-    }
+    tile_input_bwd(dp, rows, X, rec, TOKF, F_DX0);
 }
 constexpr size_t BWD_TILE_LDS = sizeof(float) * (2 * TM * XLD + TM * FLD + 2 * TM * RH * PLD);
 
@@ -444,8 +497,24 @@ __device__ __forceinline__ void cross_bwd(const Drop& dp, const unsigned long lo
     }
 }
 
-__device__ __forceinline__ void add64(float* X, const float* A) {
-    for (int e = threadIdx.x; e < TM * RD; e += NT) X[(e / RD) * XLD + e % RD] += A[(e / RD) * XLD + e % RD];
+// cross-attention (site0: its probabilities; site0 + 1: the block's output, as cross_block_fwd numbers them): dO = dV2 Wo, the
+// probabilities again from the saved q (U: q [64][XLD], then dq [64][XLD] behind it), d(K | V) of the mixed memory into dkv
+template <class Drop, class Rows>
+__device__ __forceinline__ void cross_block_bwd(const Drop& dp, uint32_t site0, const Rows& rows, CrossBwdRec f, const TileTab& tb, int n_row, int K,
+                                                int Ls, int n_rows, int n_pair, int l, const int64_t* __restrict__ src,
+                                                const float* __restrict__ ckv, const float* P, const int64_t* lo, float eps, float* X, float* T,
+                                                float* U, float* PS, float* DS, unsigned long long* KM, float* __restrict__ dkv, float scale,
+                                                float* rec, int tf, int nrec) {
+    out_proj_bwd(dp, site0 + 1, rows, f.n, P, lo, D_CAOUTW, D_N2W, eps, X, T, DS, rec, tf, nrec);
+    load64(U, XLD, rec, f.q, RD, tf, nrec);
+    __syncthreads();
+    const float* cb = P + lo[D_CAINB];
+    cross_probs(dp, site0, KM, tb, n_row, K, Ls, n_rows, l, src, ckv, cb, U, PS, scale);
+    float* DQ = U + TM * XLD;
+    cross_bwd(dp, KM, tb, n_row, K, Ls, n_rows, n_pair, l, src, ckv, cb, U, T, PS, DS, DQ, dkv, scale);
+    __syncthreads();
+    KeepRec{rec, tf, nrec}.save(DQ, XLD, f.dq, RD);
+    add_dx<RD>(DQ, XLD, P + lo[D_CAINW], X, T);
 }
 
 template <class... D>      // D: nothing (eval mode) or DropPhilox
@@ -539,81 +608,15 @@ __global__ __launch_bounds__(NT) void k_rsb_dec_tile(const float* __restrict__ P
     for (int l = RNL - 1; l >= 0; --l) {
         const int64_t* lo = off.o + T_DEC + 18 * l;
         const int f = l * LFD;
-        ln_bwd64(X, rec, f + R_V3, P + lo[D_N3W], eps, f + R_G3, f + R_Y3, f + R_DV3, TOKD);
-        __syncthreads();
-        if constexpr (Drop::on) {          // DS is free between two attention blocks: the dropped gradient is the linear's dY
-            drop_grad64(dp, rs_site(ST_DEC, l, 5), rows, X, DS, rec, TOKD, f + R_DV3, TM);
-            __syncthreads();
-            gemm_dx<RD, 4>(DS, XLD, P + lo[D_W2], U, FLD);
-        } else {
-            gemm_dx<RD, 4>(X, XLD, P + lo[D_W2], U, FLD);
-        }
-        __syncthreads();
-        if constexpr (Drop::on) {
-            gelu_bwd64(dp, rs_site(ST_DEC, l, 4), rows, U, rec, TOKD, f + R_HP, f + R_DHP, TM);
-        } else {
-            for (int e = threadIdx.x; e < TM * RF; e += NT) {
-                const int s = e / RF, c = e % RF;
-                const float d = U[s * FLD + c] * gelu_grad_exact(rec[(size_t)s * TOKD + f + R_HP + c]);
-                U[s * FLD + c] = d;
-                rec[(size_t)s * TOKD + f + R_DHP + c] = d;
-            }
-        }
-        __syncthreads();
-        gemm_dx<RF, 1>(U, FLD, P + lo[D_W1], Tt, XLD);
-        __syncthreads();
-        add64(X, Tt);
-        __syncthreads();
-        ln_bwd64(X, rec, f + R_V2, P + lo[D_N2W], eps, f + R_G2, f + R_Y2, f + R_DV2, TOKD);
-        __syncthreads();
-        // cross-attention: dO = dV2 Wo, then the probabilities again from the saved q
-        if constexpr (Drop::on) {
-            drop_grad64(dp, rs_site(ST_DEC, l, 3), rows, X, DS, rec, TOKD, f + R_DV2, TM);
-            __syncthreads();
-            gemm_dx<RD, 1>(DS, XLD, P + lo[D_CAOUTW], Tt, XLD);
-        } else {
-            gemm_dx<RD, 1>(X, XLD, P + lo[D_CAOUTW], Tt, XLD);
-        }
-        load64(U, XLD, rec, f + R_QC, RD, TOKD);
-        __syncthreads();
-        const float* cb = P + lo[D_CAINB];
-        cross_probs(dp, rs_site(ST_DEC, l, 2), KM, tb, n_row, K, Ls, n_rows, l, src, ckv, cb, U, PS, scale);
-        float* DQ = U + TM * XLD;
-        cross_bwd(dp, KM, tb, n_row, K, Ls, n_rows, n_pair, l, src, ckv, cb, U, Tt, PS, DS, DQ, dkv, scale);
-        __syncthreads();
-        keep.save(DQ, XLD, f + R_DQC, RD);
-        gemm_dx<RD, 1>(DQ, XLD, P + lo[D_CAINW], Tt, XLD);
-        __syncthreads();
-        add64(X, Tt);
-        __syncthreads();
-        ln_bwd64(X, rec, f + R_V1, P + lo[D_N1W], eps, f + R_G1, f + R_Y1, f + R_DV1, TOKD);
-        __syncthreads();
-        if constexpr (Drop::on) {
-            drop_grad64(dp, rs_site(ST_DEC, l, 1), rows, X, DS, rec, TOKD, f + R_DV1, TM);
-            __syncthreads();
-            gemm_dx<RD, 1>(DS, XLD, P + lo[D_SAOUTW], Tt, XLD);
-        } else {
-            gemm_dx<RD, 1>(X, XLD, P + lo[D_SAOUTW], Tt, XLD);
-        }
-        load64(U, QLD, rec, f + R_QKV, 3 * RD, TOKD);
-        __syncthreads();
-        self_attention_bwd(dp, rs_site(ST_DEC, l, 0), tb, U, Tt, PS, DS, rec + f + R_DQKV, scale, TOKD);
-        __syncthreads();
-        load64(U, QLD, rec, f + R_DQKV, 3 * RD, TOKD);
-        __syncthreads();
-        gemm_dx<3 * RD, 1>(U, QLD, P + lo[D_SAINW], Tt, XLD);
-        __syncthreads();
-        add64(X, Tt);
-        __syncthreads();
+        ffn_block_bwd(dp, rs_site(ST_DEC, l, 4), rows, {{f + R_V3, f + R_G3, f + R_Y3, f + R_DV3}, f + R_HP, f + R_DHP}, P, lo, D_W1, D_W2, D_N3W,
+                      eps, X, Tt, U, DS, rec, TOKD, TM);
+        cross_block_bwd(dp, rs_site(ST_DEC, l, 2), rows, {{f + R_V2, f + R_G2, f + R_Y2, f + R_DV2}, f + R_QC, f + R_DQC}, tb, n_row, K, Ls, n_rows,
+                        n_pair, l, src, ckv, P, lo, eps, X, Tt, U, PS, DS, KM, dkv, scale, rec, TOKD, TM);
+        self_block_bwd(dp, rs_site(ST_DEC, l, 0), rows, {{f + R_V1, f + R_G1, f + R_Y1, f + R_DV1}, f + R_QKV, f + R_DQKV}, P, lo, D_SAINW, D_SAOUTW,
+                       D_N1W, eps, X, Tt, U, DS, rec, TOKD, TM,
+                       [&] { self_attention_bwd(dp, rs_site(ST_DEC, l, 0), tb, U, Tt, PS, DS, rec + f + R_DQKV, scale, TOKD); });
     }
-    if constexpr (Drop::on) {              // both embedding terms went through the tgt_emb mask: so does their gradient
-        drop_tile<RD>(dp, DR4SR_REGEN_SITE_TGT_EMB, X, XLD, rows);
-        __syncthreads();
-    }
-    for (int e = threadIdx.x; e < TM * RD; e += NT) {
-        const int s = e / RD, c = e % RD;
-        rec[(size_t)s * TOKD + R_DX0 + c] = tb.tok_row[s] >= 0 ? X[s * XLD + c] : 0.f;
-    }
+    tile_input_bwd(dp, rows, X, rec, TOKD, R_DX0);
 }
 constexpr size_t DROP_KM_LDS = sizeof(unsigned long long) * TM * RH;      // the decoder tile's keep bits, behind DS (train mode only)
 
@@ -645,6 +648,57 @@ constexpr int S_VN = RNL * LF, S_GN = S_VN + 64, S_YN = S_GN + 64, S_MEMN = S_YN
               TOKS = S_DX0 + 64;
 static_assert(TOKS % 4 == 0, "source record layout");
 constexpr int ALD = 2 * RD + 4;
+
+// backward of the source side's self-attention (src_probs + src_context): q | k | v [64][QLD] and dO [64][XLD] in LDS -> dQKV of the
+// `nrec` records (gout = record base + field).  S takes the undropped probabilities again, DSb the score gradients.
+template <class Drop>
+__device__ __forceinline__ void src_attention_bwd(const Drop& dp, uint32_t site, int64_t pair, const float* QKV, const float* dO, float* S, float* DSb,
+                                                  const int* ids, int n, int causal, float* gout, float scale, int tf, int nrec) {
+    src_probs(dp, site, pair, false, QKV, S, ids, n, causal, scale);
+    for (int e = threadIdx.x; e < RH * n * n; e += NT) {
+        const int h = e / (n * n), i = (e / n) % n, j = e % n;
+        const float* go = dO + i * XLD + h * RDH;
+        const float* v = QKV + j * QLD + 2 * RD + h * RDH;
+        float a = 0.f;
+        for (int d = 0; d < RDH; ++d) a = fmaf(go[d], v[d], a);
+        DSb[(h * LMAX + i) * LMAX + j] = a;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < RH * n; e += NT) {
+        const float* pr = S + ((e / n) * LMAX + e % n) * LMAX;
+        float* ds = DSb + ((e / n) * LMAX + e % n) * LMAX;
+        float dsum = 0.f;
+        if constexpr (Drop::on) {          // dP = (dO . V) keep; the Jacobian on the undropped p; S then takes the dropped p for dV
+            float* pw = S + ((e / n) * LMAX + e % n) * LMAX;
+            const uint64_t km = prob_keep_bits(dp, site, pair, e / n, e % n, n);
+            for (int j = 0; j < n; ++j) {
+                ds[j] = ((km >> j) & 1) ? ds[j] * dp.k.scale : 0.f;
+                dsum = fmaf(pr[j], ds[j], dsum);
+            }
+            for (int j = 0; j < n; ++j) {
+                ds[j] = pr[j] * (ds[j] - dsum) * scale;
+                pw[j] = ((km >> j) & 1) ? pr[j] * dp.k.scale : 0.f;
+            }
+        } else {
+            for (int j = 0; j < n; ++j) dsum = fmaf(pr[j], ds[j], dsum);
+            for (int j = 0; j < n; ++j) ds[j] = pr[j] * (ds[j] - dsum) * scale;
+        }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < nrec * RD; e += NT) {
+        const int i = e / RD, c = e % RD, h = c / RDH;
+        float dq = 0.f, dk = 0.f, dv = 0.f;
+        if (i < n) {
+            for (int j = 0; j < n; ++j) {
+                dq = fmaf(DSb[(h * LMAX + i) * LMAX + j], QKV[j * QLD + RD + c], dq);
+                dk = fmaf(DSb[(h * LMAX + j) * LMAX + i], QKV[j * QLD + c], dk);
+                dv = fmaf(S[(h * LMAX + j) * LMAX + i], dO[j * XLD + c], dv);
+            }
+        }
+        float* rr = gout + (size_t)i * tf;
+        rr[c] = dq; rr[RD + c] = dk; rr[2 * RD + c] = dv;
+    }
+}
 
 template <int KC, class... D>      // D: nothing (eval mode) or DropPhilox
 __global__ __launch_bounds__(NT) void k_rsb_source(const float* __restrict__ P, ScoreOff off, float eps, int n_rows,
@@ -740,99 +794,20 @@ __global__ __launch_bounds__(NT) void k_rsb_source(const float* __restrict__ P, 
     for (int l = RNL - 1; l >= 0; --l) {
         const int64_t* lo = off.o + T_ENC + 12 * l;
         const int f = l * LF;
-        ln_bwd64(X, rec, f + F_V2, P + lo[E_N2W], eps, f + F_G2, f + F_Y2, f + F_DV2, TOKS, Ls);
-        __syncthreads();
-        if constexpr (Drop::on) {          // T is free until the next GEMM fills it
-            drop_grad64(dp, rs_site(ST_SRC, l, 3), rows, X, T, rec, TOKS, f + F_DV2, Ls);
-            __syncthreads();
-            gemm_dx<RD, 4>(T, XLD, P + lo[E_W2], U, FLD);
-        } else {
-            gemm_dx<RD, 4>(X, XLD, P + lo[E_W2], U, FLD);
-        }
-        __syncthreads();
-        if constexpr (Drop::on) {
-            gelu_bwd64(dp, rs_site(ST_SRC, l, 2), rows, U, rec, TOKS, f + F_HP, f + F_DHP, Ls);
-        } else {
-            for (int e = threadIdx.x; e < Ls * RF; e += NT) {
-                const int s = e / RF, c = e % RF;
-                const float d = U[s * FLD + c] * gelu_grad_exact(rec[(size_t)s * TOKS + f + F_HP + c]);
-                U[s * FLD + c] = d;
-                rec[(size_t)s * TOKS + f + F_DHP + c] = d;
-            }
-        }
-        __syncthreads();
-        gemm_dx<RF, 1>(U, FLD, P + lo[E_W1], T, XLD);
-        __syncthreads();
-        add64(X, T);
-        __syncthreads();
-        ln_bwd64(X, rec, f + F_V1, P + lo[E_N1W], eps, f + F_G1, f + F_Y1, f + F_DV1, TOKS, Ls);
-        __syncthreads();
-        if constexpr (Drop::on) {          // S (behind q | k | v) is free until src_probs fills it
-            drop_grad64(dp, rs_site(ST_SRC, l, 1), rows, X, S, rec, TOKS, f + F_DV1, Ls);
-            __syncthreads();
-            gemm_dx<RD, 1>(S, XLD, P + lo[E_OUTW], T, XLD);
-        } else {
-            gemm_dx<RD, 1>(X, XLD, P + lo[E_OUTW], T, XLD);              // dO
-        }
-        load64(QKV, QLD, rec, f + F_QKV, 3 * RD, TOKS, Ls);
-        __syncthreads();
-        src_probs(dp, rs_site(ST_SRC, l, 0), gpair, false, QKV, S, ids, n, causal, scale);
-        for (int e = threadIdx.x; e < RH * n * n; e += NT) {
-            const int h = e / (n * n), i = (e / n) % n, j = e % n;
-            const float* go = T + i * XLD + h * RDH;
-            const float* v = QKV + j * QLD + 2 * RD + h * RDH;
-            float a = 0.f;
-            for (int d = 0; d < RDH; ++d) a = fmaf(go[d], v[d], a);
-            DSb[(h * LMAX + i) * LMAX + j] = a;
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < RH * n; e += NT) {
-            const float* pr = S + ((e / n) * LMAX + e % n) * LMAX;
-            float* ds = DSb + ((e / n) * LMAX + e % n) * LMAX;
-            float dsum = 0.f;
-            if constexpr (Drop::on) {          // dP = (dO . V) keep; the Jacobian on the undropped p; S then takes the dropped p for dV
-                float* pw = S + ((e / n) * LMAX + e % n) * LMAX;
-                const uint64_t km = prob_keep_bits(dp, rs_site(ST_SRC, l, 0), gpair, e / n, e % n, n);
-                for (int j = 0; j < n; ++j) {
-                    ds[j] = ((km >> j) & 1) ? ds[j] * dp.k.scale : 0.f;
-                    dsum = fmaf(pr[j], ds[j], dsum);
-                }
-                for (int j = 0; j < n; ++j) {
-                    ds[j] = pr[j] * (ds[j] - dsum) * scale;
-                    pw[j] = ((km >> j) & 1) ? pr[j] * dp.k.scale : 0.f;
-                }
-            } else {
-                for (int j = 0; j < n; ++j) dsum = fmaf(pr[j], ds[j], dsum);
-                for (int j = 0; j < n; ++j) ds[j] = pr[j] * (ds[j] - dsum) * scale;
-            }
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < Ls * RD; e += NT) {
-            const int i = e / RD, c = e % RD, h = c / RDH;
-            float dq = 0.f, dk = 0.f, dv = 0.f;
-            if (i < n) {
-                for (int j = 0; j < n; ++j) {
-                    dq = fmaf(DSb[(h * LMAX + i) * LMAX + j], QKV[j * QLD + RD + c], dq);
-                    dk = fmaf(DSb[(h * LMAX + j) * LMAX + i], QKV[j * QLD + c], dk);
-                    dv = fmaf(S[(h * LMAX + j) * LMAX + i], T[j * XLD + c], dv);
-                }
-            }
-            float* rr = rec + (size_t)i * TOKS + f + F_DQKV;
-            rr[c] = dq; rr[RD + c] = dk; rr[2 * RD + c] = dv;
-        }
-        __syncthreads();
-        load64(QKV, QLD, rec, f + F_DQKV, 3 * RD, TOKS, Ls);
-        __syncthreads();
-        gemm_dx<3 * RD, 1>(QKV, QLD, P + lo[E_INW], T, XLD);
-        __syncthreads();
-        add64(X, T);
-        __syncthreads();
+        // KEPT DIFFERENCE: no idle buffer for the dropped gradient here.  The FFN lends T, free until the GEMM through W1 fills it; the
+        // self-attention lends S (behind q | k | v), free until src_probs fills it, because T is the out-projection's output
+        ffn_block_bwd(dp, rs_site(ST_SRC, l, 2), rows, {{f + F_V2, f + F_G2, f + F_Y2, f + F_DV2}, f + F_HP, f + F_DHP}, P, lo, E_W1, E_W2, E_N2W,
+                      eps, X, T, U, T, rec, TOKS, Ls);
+        self_block_bwd(dp, rs_site(ST_SRC, l, 0), rows, {{f + F_V1, f + F_G1, f + F_Y1, f + F_DV1}, f + F_QKV, f + F_DQKV}, P, lo, E_INW, E_OUTW,
+                       E_N1W, eps, X, T, U, S, rec, TOKS, Ls, [&] {
+                           src_attention_bwd(dp, rs_site(ST_SRC, l, 0), gpair, QKV, T, S, DSb, ids, n, causal, rec + f + F_DQKV, scale, TOKS, Ls);
+                       });
     }
     if constexpr (Drop::on) {              // both embedding terms went through the src_emb mask: so does their gradient
         drop_tile<RD>(dp, DR4SR_REGEN_SITE_SRC_EMB, X, XLD, rows);
         __syncthreads();
     }
-    keep.save(X, XLD, S_DX0, RD);
+    keep.save(X, XLD, S_DX0, RD);           // KEPT DIFFERENCE: the Ls records of the pair only (tile_input_bwd writes all 64 slots)
 }
 template <int KC> constexpr size_t bwd_source_lds() {
     constexpr int CLD = KC * RD + 4;
