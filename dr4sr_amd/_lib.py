@@ -276,6 +276,7 @@ SYMBOLS = {
                                                   C.c_int32, _f32p, C.c_int64, C.c_void_p]),
     "dr4sr_full_score_topk_ws": (C.c_int, [_f32p, _f32p, _i64p, _f32p, _i64p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            _f32p, C.c_int64, C.c_void_p]),
+    "dr4sr_full_score_topk_form": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),          # test hook (include/dr4sr_hip_hooks.h)
     # ABI 8: the data-parallel transport (csrc/comm.hip, RCCL on the caller's stream); comm handles are opaque pointers
     "dr4sr_comm_unique_id": (C.c_int, [C.c_void_p]),
     "dr4sr_comm_init_rank": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),

@@ -388,6 +388,10 @@ __global__ __launch_bounds__(256) void k_topk_select(float* __restrict__ S, cons
     }
 }
 
+// a history word as a 32-bit id for the candidate kernels' compares: a word outside [0, 2^31) names no item (-1 matches no emitted id).
+// A plain (int) cast would make 2^32 + id hit item id, which the per-row and two-kernel forms ignore.
+__device__ __forceinline__ int hist_id32(int64_t h) { return (h >= 0 && h <= 0x7fffffffll) ? (int)h : -1; }
+
 // ---- wave-per-row selection (fused form): no workgroup barrier anywhere.  A barrier costs ~0.5-1 us with eight workgroups per CU and
 // the workgroup forms above cross 50-80 of them per row; one wave serves its LDS operations in order, so a wave-private histogram
 // needs none.
@@ -467,12 +471,12 @@ __global__ __launch_bounds__(64) void k_cand_select_w(unsigned long long* __rest
     if (nc > CAPC || *overflow) { if (lane == 0) atomicExch(overflow, 1); return; }       // (an overflowed batch is redone by the two-kernel form)
     unsigned long long* cg = cand_g + (size_t)b * CAPC;
     const int Lc = Lh < 128 ? Lh : 128;
-    for (int j = lane; j < Lc; j += 64) hl[j] = (int)hist[(size_t)b * Lh + j];
+    for (int j = lane; j < Lc; j += 64) hl[j] = hist_id32(hist[(size_t)b * Lh + j]);
     for (int i = lane; i < nc; i += 64) {                  // history -> dropped (key 0 sorts below every real score)
         const int id = (int)(~(unsigned)cg[i]);
         bool hit = false;
         for (int j = 0; j < Lc; ++j) hit |= hl[j] == id;
-        for (int j = Lc; j < Lh; ++j) hit |= (int)hist[(size_t)b * Lh + j] == id;
+        for (int j = Lc; j < Lh; ++j) hit |= hist_id32(hist[(size_t)b * Lh + j]) == id;
         if (hit) cg[i] = 0ull;
     }
     __threadfence_block();
@@ -533,7 +537,7 @@ __global__ __launch_bounds__(256) void k_cand_select(const unsigned long long* _
     const int b = blockIdx.x, tid = threadIdx.x;
     const int nc = cnt[b];
     if (nc > CAPC || *overflow) { if (tid == 0) atomicExch(overflow, 1); return; }      // (an overflowed batch is redone by the two-kernel form)
-    for (int j = tid; j < Lh; j += 256) hl[j] = (int)hist[(size_t)b * Lh + j];
+    for (int j = tid; j < Lh; j += 256) hl[j] = hist_id32(hist[(size_t)b * Lh + j]);
     __syncthreads();
     int ns = 128;
     while (ns < nc) ns <<= 1;
@@ -573,34 +577,63 @@ extern "C" int64_t dr4sr_full_score_topk_workspace_bytes(int64_t B, int32_t n_it
     return B * (int64_t)((n_items + 63) / 64 * 64) * 4 + 256;     // [B][lds_s] scores + the fused form's overflow flag behind them
 }
 
-static int topk_ws_impl(const float* q, const float* E, const int64_t* hist, const uint8_t* blocked, float* out_score, int64_t* out_item,
-                        int64_t B, int32_t D, int32_t n_items, int32_t Lh, int32_t k, float* workspace,
-                        int64_t workspace_bytes, void* stream) {
-    if (!q || !E || !out_score || !out_item || !workspace || B < 0 || n_items < 2 || k <= 0 || k > 128 || Lh < 0 || (Lh > 0 && !hist))
-        return DR4SR_E_ARG;
-    if (D != 64 && D != 128) return DR4SR_E_SHAPE;
-    const int lds_s = (n_items + 63) / 64 * 64;
-    if (workspace_bytes < B * (int64_t)lds_s * 4) return DR4SR_E_WS;
-    const size_t lds_fix = sizeof(int) * (256 + 8) + sizeof(unsigned long long) * 512;
-    const size_t lds_row = sizeof(unsigned) * ((n_items + 3) & ~3) + lds_fix;
+// Which launch forms the workspace calls take: the ONE place that decides it (topk_ws_impl dispatches on it, the test hook
+// dr4sr_full_score_topk_form reports it).  err != 0: what the call returns for these sizes.
+constexpr int TOPK_CAPC = 2048, TOPK_STRIDE = 8;
+struct TopkForm {
+    int err;
+    bool fused, ldsrow;
+    int lds_s, n_sub, sub_s;
+    size_t lds_fix, lds_row;
+    int64_t flag_off;
+};
+static TopkForm topk_form(int64_t B, int32_t D, int32_t n_items, int32_t Lh, int32_t k, int64_t workspace_bytes) {
+    TopkForm f{};
+    if (B < 0 || n_items < 2 || k <= 0 || k > 128 || Lh < 0) { f.err = DR4SR_E_ARG; return f; }
+    if (D != 64 && D != 128) { f.err = DR4SR_E_SHAPE; return f; }
+    f.lds_s = (n_items + 63) / 64 * 64;
+    if (workspace_bytes < B * (int64_t)f.lds_s * 4) { f.err = DR4SR_E_WS; return f; }
+    f.lds_fix = sizeof(int) * (256 + 8) + sizeof(unsigned long long) * 512;
+    f.lds_row = sizeof(unsigned) * ((n_items + 3) & ~3) + f.lds_fix;
     const int lds_max_kb = DR4SR_XENV("DR4SR_TOPK_LDS_KB") ? atoi(DR4SR_XENV("DR4SR_TOPK_LDS_KB")) : 24;      // measured: above ~4 k items the LDS copy costs more occupancy than the second row read (0.120 vs 0.104 ms at N = 11 925)
-    const bool ldsrow = lds_row <= (size_t)lds_max_kb * 1024;               // (above that the LDS copy costs more occupancy than the second row read)
-    if (B == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid(lds_s / 64, (unsigned)((B + 63) / 64));
-    const size_t lds_g = sizeof(float) * 2 * 64 * (D + 1);
-    FuseArgs Fz{};
+    f.ldsrow = f.lds_row <= (size_t)lds_max_kb * 1024;               // (above that the LDS copy costs more occupancy than the second row read)
     // ---- fused form: catalogs of >= 4 096 items, k * stride candidates expected per row
     // Measured (2048 x 11 925, k = 100, tools/topk_probe.py): the fused form moves ~50 MB instead of 332 MB but takes 167 us against the
     // two-kernel form's 104 us (subset pass 38, emit 85, candidate select 40: per-row LDS counters in the GEMM epilogue and 2048 small
     // selection waves cost more than the 97 MB matrix round trip at 3.2 TB/s); at N = 200 000 1.3-1.8 ms against 1.55 ms.  It is
     // therefore OPT-IN (DR4SR_TOPK_FUSED=1; cached until dr4sr_reload_env()) until the emit epilogue is cheaper; the tests run both forms.
     const bool unfused = DR4SR_ENV("DR4SR_TOPK_FUSED") == nullptr;
-    constexpr int CAPC = 2048;
-    const int stride = 8, n_sub = (n_items - 1 + stride - 1) / stride, sub_s = (n_sub + 63) / 64 * 64;
-    const int64_t need = B * ((int64_t)sub_s * 4 + (int64_t)CAPC * 8 + 8) + 256;
-    const int64_t flag_off = B * (int64_t)lds_s * 4;       // BEHIND the [B][lds_s] matrix: the two-kernel fall-back of an overflowed batch
-    const bool fused = !unfused && n_items >= 4096 && need <= flag_off && flag_off + 4 <= workspace_bytes && k * stride * 2 <= CAPC;     //  writes its scores over everything else
+    f.n_sub = (n_items - 1 + TOPK_STRIDE - 1) / TOPK_STRIDE;
+    f.sub_s = (f.n_sub + 63) / 64 * 64;
+    const int64_t need = B * ((int64_t)f.sub_s * 4 + (int64_t)TOPK_CAPC * 8 + 8) + 256;
+    f.flag_off = B * (int64_t)f.lds_s * 4;                 // BEHIND the [B][lds_s] matrix: the two-kernel fall-back of an overflowed batch
+    f.fused = !unfused && n_items >= 4096 && need <= f.flag_off && f.flag_off + 4 <= workspace_bytes && k * TOPK_STRIDE * 2 <= TOPK_CAPC;     //  writes its scores over everything else
+    return f;
+}
+
+extern "C" int dr4sr_full_score_topk_form(int64_t B, int32_t D, int32_t n_items, int32_t Lh, int32_t k, int64_t workspace_bytes) {
+    const TopkForm f = topk_form(B, D, n_items, Lh, k, workspace_bytes);
+    return f.err ? f.err : (f.fused ? 1 : 0) | (f.ldsrow ? 2 : 0);
+}
+
+static int topk_ws_impl(const float* q, const float* E, const int64_t* hist, const uint8_t* blocked, float* out_score, int64_t* out_item,
+                        int64_t B, int32_t D, int32_t n_items, int32_t Lh, int32_t k, float* workspace,
+                        int64_t workspace_bytes, void* stream) {
+    if (!q || !E || !out_score || !out_item || !workspace || (Lh > 0 && !hist)) return DR4SR_E_ARG;
+    const TopkForm form = topk_form(B, D, n_items, Lh, k, workspace_bytes);
+    if (form.err) return form.err;
+    const int lds_s = form.lds_s;
+    const size_t lds_fix = form.lds_fix, lds_row = form.lds_row;
+    const bool ldsrow = form.ldsrow;
+    if (B == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid(lds_s / 64, (unsigned)((B + 63) / 64));
+    const size_t lds_g = sizeof(float) * 2 * 64 * (D + 1);
+    FuseArgs Fz{};
+    constexpr int CAPC = TOPK_CAPC;
+    const int stride = TOPK_STRIDE, n_sub = form.n_sub, sub_s = form.sub_s;
+    const int64_t flag_off = form.flag_off;
+    const bool fused = form.fused;
     const int* run_if = nullptr;
     if (fused) {
         // workspace: [B][sub_s] subset scores | [B] bound | [B] counters | [B][CAPC] candidates  (the two-kernel fall-back, which only

@@ -74,6 +74,15 @@ int dr4sr_gru4rec_launch_kernel(const dr4sr_gru4rec_plan* plan, int32_t kernel, 
 #define DR4SR_FK_WGRAD      4
 int dr4sr_fmlp_launch_kernel(const dr4sr_fmlp_plan* plan, int32_t kernel, int32_t layer, void* stream);
 
+/* which launch forms dr4sr_full_score_topk[_masked]_ws takes for these arguments under the current environment:
+ * bit 0 = fused (subset bound -> emit -> wave-per-row select), bit 1 = the selection keeps the row in LDS.  < 0: the error the call would return.
+ * Computed by the predicate the calls themselves dispatch on (csrc/topk.hip topk_form).
+ * After a FUSED call has run, the int32 at byte offset B * lds_s * 4 of the workspace (lds_s = n_items rounded up to a multiple of 64)
+ * is the batch's overflow flag: 0 = the candidate path produced the output, 1 = a row overflowed a candidate buffer (more than 80
+ * candidates in a 512-item chunk, more than 2048 in the row, or more than 128 survivors tied at the k-th score) and the whole batch was
+ * redone by the two-kernel form.  A call that is not fused does not write the word. */
+int dr4sr_full_score_topk_form(int64_t B, int32_t D, int32_t n_items, int32_t Lh, int32_t k, int64_t workspace_bytes);
+
 /* Measurement hook of bench.py (the driver's contract is ONE JSON line on stdout): keep a COMPLETE line ready, and if the process is
  * then killed by a fatal signal (SIGABRT from a foreign thread's uncaught exception, SIGSEGV / SIGBUS / SIGFPE / SIGILL, or the SIGTERM
  * a launcher sends to the surviving ranks when another rank died) write it to `fd` and _exit(exit_code) from the signal handler —
