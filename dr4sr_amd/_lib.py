@@ -77,28 +77,32 @@ _f32p = C.c_void_p
 _i64p = C.c_void_p
 
 
+# The three training plans of include/dr4sr_hip.h are mostly the same fields in the same order; the blocks they share, in struct order:
+_PLAN_BUFFERS = [("seed", C.c_uint64),
+                 ("params", _f32p), ("grads", _f32p), ("adam_m", _f32p), ("adam_v", _f32p),
+                 ("n_params", C.c_int64)]
+_PLAN_WORKSPACE = [("sample_neg", C.c_int32),
+                   ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                   ("state", C.c_void_p)]
+_PLAN_OPTIMIZER = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("adam_eps", C.c_float), ("weight_decay", C.c_float)]
+_PLAN_PERM_LOG = [("perm", _i64p), ("n_perm", C.c_int64), ("perm_stride", C.c_int64), ("perm_offset", C.c_int64),
+                  ("perm_counter", C.c_void_p),
+                  ("loss_log", _f32p)]
+
+
+def _i32(*names):
+    return [(n, C.c_int32) for n in names]
+
+
+def _ptrs(*names):
+    return [(n, _i64p) for n in names]
+
+
 class SasrecPlan(C.Structure):
-    """mirror of `dr4sr_sasrec_plan` (include/dr4sr_hip.h)"""
-    _fields_ = [
-        ("abi_version", C.c_int32),
-        ("B", C.c_int32), ("L", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("F", C.c_int32),
-        ("n_layer", C.c_int32), ("n_items", C.c_int32),
-        ("ln_eps", C.c_float), ("p_drop", C.c_float),
-        ("seed", C.c_uint64),
-        ("params", _f32p), ("grads", _f32p), ("adam_m", _f32p), ("adam_v", _f32p),
-        ("n_params", C.c_int64),
-        ("in_item_id", _i64p), ("item_id", _i64p), ("seqlen", _i64p), ("rows", _i64p), ("neg_item", _i64p),
-        ("sample_neg", C.c_int32),
-        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-        ("state", C.c_void_p),
-        ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("adam_eps", C.c_float),
-        ("weight_decay", C.c_float),
-        ("perm", _i64p), ("n_perm", C.c_int64), ("perm_stride", C.c_int64), ("perm_offset", C.c_int64),
-        ("perm_counter", C.c_void_p),
-        ("loss_log", _f32p),
-        ("expected_tokens", C.c_int32),
-        ("optimizer", C.c_int32),
-    ]
+    """mirror of `dr4sr_sasrec_plan` (include/dr4sr_hip.h); the only plan that ends ..., loss_log, expected_tokens, optimizer"""
+    _fields_ = (_i32("abi_version", "B", "L", "D", "H", "F", "n_layer", "n_items") + [("ln_eps", C.c_float), ("p_drop", C.c_float)]
+                + _PLAN_BUFFERS + _ptrs("in_item_id", "item_id", "seqlen", "rows", "neg_item") + _PLAN_WORKSPACE + _PLAN_OPTIMIZER
+                + _PLAN_PERM_LOG + _i32("expected_tokens", "optimizer"))
 
 
 class MetaWeighting(C.Structure):
@@ -108,47 +112,17 @@ class MetaWeighting(C.Structure):
 
 
 class FmlpPlan(C.Structure):
-    """mirror of `dr4sr_fmlp_plan` (include/dr4sr_hip.h)"""
-    _fields_ = [
-        ("abi_version", C.c_int32),
-        ("B", C.c_int32), ("L", C.c_int32), ("D", C.c_int32), ("F", C.c_int32), ("n_layer", C.c_int32), ("n_items", C.c_int32),
-        ("ln_eps", C.c_float), ("p_drop", C.c_float),
-        ("seed", C.c_uint64),
-        ("params", _f32p), ("grads", _f32p), ("adam_m", _f32p), ("adam_v", _f32p),
-        ("n_params", C.c_int64),
-        ("in_item_id", _i64p), ("item_id", _i64p), ("rows", _i64p), ("neg_item", _i64p),
-        ("sample_neg", C.c_int32),
-        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-        ("state", C.c_void_p),
-        ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("adam_eps", C.c_float),
-        ("weight_decay", C.c_float),
-        ("optimizer", C.c_int32),
-        ("perm", _i64p), ("n_perm", C.c_int64), ("perm_stride", C.c_int64), ("perm_offset", C.c_int64),
-        ("perm_counter", C.c_void_p),
-        ("loss_log", _f32p),
-    ]
+    """mirror of `dr4sr_fmlp_plan` (include/dr4sr_hip.h): no H, no seqlen"""
+    _fields_ = (_i32("abi_version", "B", "L", "D", "F", "n_layer", "n_items") + [("ln_eps", C.c_float), ("p_drop", C.c_float)]
+                + _PLAN_BUFFERS + _ptrs("in_item_id", "item_id", "rows", "neg_item") + _PLAN_WORKSPACE + _PLAN_OPTIMIZER
+                + _i32("optimizer") + _PLAN_PERM_LOG)
 
 
 class GruPlan(C.Structure):
-    """mirror of `dr4sr_gru4rec_plan` (include/dr4sr_hip.h)"""
-    _fields_ = [
-        ("abi_version", C.c_int32),
-        ("B", C.c_int32), ("L", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("n_layer", C.c_int32), ("n_items", C.c_int32),
-        ("p_drop", C.c_float),
-        ("seed", C.c_uint64),
-        ("params", _f32p), ("grads", _f32p), ("adam_m", _f32p), ("adam_v", _f32p),
-        ("n_params", C.c_int64),
-        ("in_item_id", _i64p), ("item_id", _i64p), ("seqlen", _i64p), ("rows", _i64p), ("neg_item", _i64p),
-        ("sample_neg", C.c_int32),
-        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-        ("state", C.c_void_p),
-        ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("adam_eps", C.c_float),
-        ("weight_decay", C.c_float),
-        ("optimizer", C.c_int32),
-        ("perm", _i64p), ("n_perm", C.c_int64), ("perm_stride", C.c_int64), ("perm_offset", C.c_int64),
-        ("perm_counter", C.c_void_p),
-        ("loss_log", _f32p),
-    ]
+    """mirror of `dr4sr_gru4rec_plan` (include/dr4sr_hip.h): no F, no ln_eps"""
+    _fields_ = (_i32("abi_version", "B", "L", "D", "H", "n_layer", "n_items") + [("p_drop", C.c_float)]
+                + _PLAN_BUFFERS + _ptrs("in_item_id", "item_id", "seqlen", "rows", "neg_item") + _PLAN_WORKSPACE + _PLAN_OPTIMIZER
+                + _i32("optimizer") + _PLAN_PERM_LOG)
 
 
 class RegenPlan(C.Structure):

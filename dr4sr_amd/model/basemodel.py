@@ -106,6 +106,26 @@ class _ScoreBCE(torch.autograd.Function):
         return None, dq, None, None, None, None
 
 
+class _Encode(torch.autograd.Function):
+    """a model's query encoder through engine.encode / engine.encode_bwd.  plan_args, plan_kw: what engine.make_plan takes besides the
+    ids ((seqlen,) where the model has lengths; SASRec's slot); enc_args: what encode takes besides the plan and the mode ((pooling,))"""
+
+    @staticmethod
+    def forward(ctx, model, anchor, idx, plan_args, plan_kw, training, enc_args):
+        eng = model.engine
+        idx, plan_args = idx.contiguous(), tuple(t.contiguous() for t in plan_args)
+        out = eng.encode(eng.make_plan(idx, None, *plan_args, **plan_kw), training, *enc_args)
+        ctx.model, ctx.args = model, (idx, plan_args, plan_kw, training, enc_args)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        idx, plan_args, plan_kw, training, enc_args = ctx.args
+        eng = ctx.model.engine
+        eng.encode_bwd(eng.make_plan(idx, None, *plan_args, **plan_kw), training, *enc_args, gout.contiguous())
+        return None, None, None, None, None, None, None
+
+
 class BaseModel(nn.Module):
     _det_set_by_model = False          # train.deterministic turned DR4SR_DETERMINISTIC on (as opposed to the user's environment)
 
@@ -758,3 +778,51 @@ class BaseModel(nn.Module):
         ckpt = torch.load(path, weights_only=False, map_location=self.device)
         self.config = ckpt["config"]
         self.load_state_dict(ckpt["parameters"])
+
+
+class FlatEngineModel(BaseModel):
+    """what the models over a FlatEngine (SASRec, GRU4Rec, FMLP) share: the engine's constructor arguments that come from the config,
+    the buffers of the fused step and the plans of a batch.  A model without lengths or pooling (FMLP) overrides the two hooks."""
+    _supports_perm_sel = True          # batch selection fused into the step's first kernel (k steps per graph, no per-step rows copy)
+    _raw_enc_args = (_lib.POOL_ORIGIN,)          # what engine.encode takes behind (plan, training) for the per-position queries
+
+    def _plan_args(self, fields):
+        """what engine.make_plan takes between the targets and rows=: the lengths of a batch dict / the dataset's fields"""
+        return (fields["seqlen"],)
+
+    def _max_batch(self, config) -> int:   # rows the engine's workspaces are sized for
+        return max(int(config["train"]["batch_size"]), int(config["eval"]["batch_size"]))
+
+    def _engine_kw(self):
+        tc = self.config["train"]
+        return dict(seed=int(tc["seed"]) + 7919 * self.rank, lr=float(tc["learning_rate"]), weight_decay=float(tc["weight_decay"]))
+
+    def _alloc_step_buffers(self, neg_per_row: int):
+        """rows[] and the sampled negatives of the fused step (captured graphs hold their addresses)"""
+        bs = int(self.config["train"]["batch_size"])
+        self._rows_buf = torch.zeros(bs, dtype=torch.int64, device=self.device)
+        self._neg_buf = torch.zeros(bs * neg_per_row, dtype=torch.int64, device=self.device)
+
+    def training_step(self, batch, reduce=True, return_query=False, align=False):
+        return super().training_step(batch, reduce, return_query)
+
+    # raw (non-autograd) hooks used by MetaModel's fused weighted step / hyper-gradient
+    def _encode_raw(self, batch, training=True):
+        eng = self.engine
+        return eng.encode(eng.make_plan(batch["in_" + self.fiid], None, *self._plan_args(batch)), training, *self._raw_enc_args)
+
+    def _encode_bwd_raw(self, batch, d_query, training=True):
+        eng = self.engine
+        eng.encode_bwd(eng.make_plan(batch["in_" + self.fiid], None, *self._plan_args(batch)), training, *self._raw_enc_args, d_query)
+
+    def _batch_plan(self, batch):
+        """plan of the fused fwd_bwd on a materialised batch with the batch's own negatives"""
+        return self.engine.make_plan(batch["in_" + self.fiid], batch[self.fiid], *self._plan_args(batch),
+                                     neg_item=batch["neg_item"].contiguous().view(-1), sample_neg=False)
+
+    def _api_plan(self):
+        return None                    # a bare optimizer step needs no plan (engine.adam_step: dr4sr_optimizer_flat)
+
+    def _train_plan(self, fields, rows, perm_sel=None, loss_log=None):
+        return self.engine.make_plan(fields["in_item_id"], fields["item_id"], *self._plan_args(fields), rows=rows, neg_item=self._neg_buf,
+                                     sample_neg=True, perm_sel=perm_sel, loss_log=loss_log)

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from ..fmlp_engine import FmlpEngine
-from .basemodel import BaseModel
+from .basemodel import FlatEngineModel, _Encode
 from .sasrec import _Embedding, _LayerNorm, _Linear, _bind
 
 
@@ -49,33 +49,18 @@ class FMLPEncoder(nn.Module):
             lyr.filterlayer.complex_weight.data.copy_(self.layer[0].filterlayer.complex_weight.data)
 
 
-class _Encode(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, anchor, idx, training):
-        eng = model.engine
-        idx = idx.contiguous()
-        out = eng.encode(eng.make_plan(idx, None), training)
-        ctx.model, ctx.args = model, (idx, training)
-        return out
+class FMLP(FlatEngineModel):
+    _raw_enc_args = ()                 # one query per row, the last position's: the engine's encode takes no pooling
 
-    @staticmethod
-    def backward(ctx, gout):
-        idx, training = ctx.args
-        eng = ctx.model.engine
-        eng.encode_bwd(eng.make_plan(idx, None), training, gout.contiguous())
-        return None, None, None, None
+    def _plan_args(self, fields):    # ... and its make_plan no lengths (left-padded rows)
+        return ()
 
-
-class FMLP(BaseModel):
     def __init__(self, config, dataset_list) -> None:
         super().__init__(config, dataset_list)
-        tc = config["train"]
         if self.embed_dim != 64 or self.max_seq_len != 50:
             raise ValueError("FMLP hard-codes embed_dim 64 and max_seq_len 50 (reference model/fmlp.py:11-12)")
-        max_b = max(int(tc["batch_size"]), int(config["eval"]["batch_size"]))
-        self.engine = FmlpEngine(self.num_items, 50, 64, 256, config["model"]["layer_num"], 1e-12, 0.5, max_b, self.device,
-                                 seed=int(tc["seed"]) + 7919 * self.rank, lr=float(tc["learning_rate"]),
-                                 weight_decay=float(tc["weight_decay"]))
+        self.engine = FmlpEngine(self.num_items, 50, 64, 256, config["model"]["layer_num"], 1e-12, 0.5, self._max_batch(config),
+                                 self.device, **self._engine_kw())
         self.device = self.engine.device
         eng = self.engine
         self.item_embedding = _Embedding(eng, "item_embedding.weight", self.num_items, 64, padding_idx=0)
@@ -83,32 +68,7 @@ class FMLP(BaseModel):
         self.LayerNorm = _LayerNorm(eng, "LayerNorm.", 64, 1e-12)
         self.dropout = nn.Dropout(0.5)
         self.item_encoder = FMLPEncoder(eng, num_hidden_layers=config["model"]["layer_num"])
-        self._rows_buf = torch.zeros(int(tc["batch_size"]), dtype=torch.int64, device=self.device)
-        self._neg_buf = torch.zeros(int(tc["batch_size"]), dtype=torch.int64, device=self.device)
+        self._alloc_step_buffers(1)
 
     def forward(self, batch, need_pooling=True):
-        return _Encode.apply(self, self.item_embedding.weight, batch["in_" + self.fiid], bool(self.training))
-
-    def training_step(self, batch, reduce=True, return_query=False, align=False):
-        return super().training_step(batch, reduce, return_query)
-
-    def _encode_raw(self, batch, training=True):
-        eng = self.engine
-        return eng.encode(eng.make_plan(batch["in_" + self.fiid], None), training)
-
-    def _encode_bwd_raw(self, batch, d_query, training=True):
-        eng = self.engine
-        eng.encode_bwd(eng.make_plan(batch["in_" + self.fiid], None), training, d_query)
-
-    def _batch_plan(self, batch):
-        return self.engine.make_plan(batch["in_" + self.fiid], batch[self.fiid],
-                                     neg_item=batch["neg_item"].contiguous().view(-1), sample_neg=False)
-
-    def _api_plan(self):
-        return None
-
-    _supports_perm_sel = True          # round 4: batch selection inside the step's first launch (k steps per graph, no per-step rows copy)
-
-    def _train_plan(self, fields, rows, perm_sel=None, loss_log=None):
-        return self.engine.make_plan(fields["in_item_id"], fields["item_id"], rows=rows, neg_item=self._neg_buf, sample_neg=True,
-                                     perm_sel=perm_sel, loss_log=loss_log)
+        return _Encode.apply(self, self.item_embedding.weight, batch["in_" + self.fiid], (), {}, bool(self.training), ())

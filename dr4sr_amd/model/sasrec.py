@@ -17,7 +17,7 @@ import torch.nn as nn
 from .. import _lib
 from ..engine import SasrecEngine
 from ..parallel import allreduce_flat, shard_bounds
-from .basemodel import BaseModel
+from .basemodel import FlatEngineModel, _Encode
 
 
 def _bind(module: nn.Module, name: str, view: torch.Tensor, grad: torch.Tensor):
@@ -77,26 +77,6 @@ class _Encoder(nn.Module):
         self.layers = nn.ModuleList([_EncoderLayer(eng, f"{prefix}layers.{i}.", D, F, eps) for i in range(n_layer)])
 
 
-class _Encode(torch.autograd.Function):
-    """SASRecQueryEncoder.forward + SeqPoolingLayer through dr4sr_sasrec_encode / _encode_bwd"""
-
-    @staticmethod
-    def forward(ctx, model, anchor, idx, seqlen, training, pooling, slot=0):
-        eng = model.engine
-        idx, seqlen = idx.contiguous(), seqlen.contiguous()
-        plan = eng.make_plan(idx, None, seqlen, slot=slot)
-        out = eng.encode(plan, training, pooling)
-        ctx.model, ctx.args = model, (idx, seqlen, training, pooling, slot)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        idx, seqlen, training, pooling, slot = ctx.args
-        eng = ctx.model.engine
-        eng.encode_bwd(eng.make_plan(idx, None, seqlen, slot=slot), training, pooling, gout.contiguous())
-        return None, None, None, None, None, None, None
-
-
 class SASRecQueryEncoder(nn.Module):
     def __init__(self, fiid, embed_dim, max_seq_len, n_head, hidden_size, dropout, activation, layer_norm_eps, n_layer,
                  item_encoder, engine: SasrecEngine, owner, bidirectional=False, training_pooling_type="origin",
@@ -132,19 +112,17 @@ class SASRecQueryEncoder(nn.Module):
         else:
             pooling = self._POOL[self.training_pooling_type if self.training else self.eval_pooling_type]
         model = self._owner[0]
-        return _Encode.apply(model, model.item_embedding.weight, batch["in_" + self.fiid], batch["seqlen"],
-                             bool(self.training), pooling, slot)
+        return _Encode.apply(model, model.item_embedding.weight, batch["in_" + self.fiid], (batch["seqlen"],), {"slot": slot},
+                             bool(self.training), (pooling,))
 
 
-class SASRec(BaseModel):
+class SASRec(FlatEngineModel):
     def __init__(self, config, dataset_list) -> None:
         super().__init__(config, dataset_list)
-        mc, tc = config["model"], config["train"]
-        max_b = self._max_batch(config)
+        mc = config["model"]
         self.engine = SasrecEngine(self._table_rows(), self.max_seq_len, self.embed_dim, mc["head_num"], mc["hidden_size"],
-                                   mc["layer_num"], mc["layer_norm_eps"], mc["dropout_rate"], max_b, self.device,
-                                   seed=int(tc["seed"]) + 7919 * self.rank, lr=float(tc["learning_rate"]),
-                                   weight_decay=float(tc["weight_decay"]), n_slots=self._n_slots())
+                                   mc["layer_num"], mc["layer_norm_eps"], mc["dropout_rate"], self._max_batch(config), self.device,
+                                   n_slots=self._n_slots(), **self._engine_kw())
         self.device = self.engine.device
         # regime hint for plans on per-batch tensors (engine._expected_tokens): mean valid length of the training split
         self.engine.mean_len = None
@@ -159,15 +137,11 @@ class SASRec(BaseModel):
         self.query_encoder = SASRecQueryEncoder(self.fiid, self.embed_dim, self.max_seq_len, mc["head_num"], mc["hidden_size"],
                                                 mc["dropout_rate"], mc["activation"], mc["layer_norm_eps"], mc["layer_num"],
                                                 self.item_embedding, self.engine, self)
-        self._rows_buf = torch.zeros(int(tc["batch_size"]), dtype=torch.int64, device=self.device)
-        self._neg_buf = torch.zeros(int(tc["batch_size"]) * self.max_seq_len, dtype=torch.int64, device=self.device)
+        self._alloc_step_buffers(self.max_seq_len)
         self._dummy = torch.ones(1, dtype=torch.int64, device=self.device)
 
     def _table_rows(self) -> int:          # rows of the item table (CL4SRec adds the mask item)
         return self.num_items
-
-    def _max_batch(self, config) -> int:   # rows the engine's workspaces are sized for
-        return max(int(config["train"]["batch_size"]), int(config["eval"]["batch_size"]))
 
     def _n_slots(self) -> int:             # forward passes alive per step
         return 1
@@ -180,29 +154,9 @@ class SASRec(BaseModel):
             raise NotImplementedError("alignment/uniformity objective (sasrec.py:110-119) is not used by any shipped config")
         return super().training_step(batch, reduce, return_query)
 
-    # raw (non-autograd) hooks used by MetaModel's fused weighted step / hyper-gradient
-    def _encode_raw(self, batch, training=True):
-        eng = self.engine
-        return eng.encode(eng.make_plan(batch["in_" + self.fiid], None, batch["seqlen"]), training, _lib.POOL_ORIGIN)
-
-    def _encode_bwd_raw(self, batch, d_query, training=True):
-        eng = self.engine
-        eng.encode_bwd(eng.make_plan(batch["in_" + self.fiid], None, batch["seqlen"]), training, _lib.POOL_ORIGIN, d_query)
-
-    def _batch_plan(self, batch):
-        """plan of the fused fwd_bwd on a materialised batch with the batch's own negatives"""
-        return self.engine.make_plan(batch["in_" + self.fiid], batch[self.fiid], batch["seqlen"],
-                                     neg_item=batch["neg_item"].contiguous().view(-1), sample_neg=False)
-
     def _api_plan(self):
         """plan of a bare optimizer step (no batch): a 1-row dummy; its id tensor is built once (expand().contiguous() is a copy
         kernel — inside a captured step it would be replayed every time)"""
         if getattr(self, "_dummy_ids", None) is None:
             self._dummy_ids = self._dummy.view(1, 1).expand(1, self.max_seq_len).contiguous()
         return self.engine.make_plan(self._dummy_ids, None, self._dummy)
-
-    _supports_perm_sel = True          # batch selection fused into the step's first kernel (no per-step rows copy)
-
-    def _train_plan(self, fields, rows, perm_sel=None, loss_log=None):
-        return self.engine.make_plan(fields["in_item_id"], fields["item_id"], fields["seqlen"], rows=rows,
-                                     neg_item=self._neg_buf, sample_neg=True, perm_sel=perm_sel, loss_log=loss_log)

@@ -123,6 +123,49 @@ def test_plan_validation_errors():
     assert lib.dr4sr_sasrec_fwd_bwd(C.byref(p), None) == -1            # perm without rows / perm_counter
 
 
+# (field, offset, size) of the three training plans in struct order, recorded from the mirrors as they stood before they were built from
+# shared blocks (ABI 10, include/dr4sr_hip.h)
+PLAN_LAYOUTS = {
+    "SasrecPlan": (240, "dr4sr_sasrec_plan_sizeof", [
+        ("abi_version", 0, 4), ("B", 4, 4), ("L", 8, 4), ("D", 12, 4), ("H", 16, 4), ("F", 20, 4), ("n_layer", 24, 4), ("n_items", 28, 4),
+        ("ln_eps", 32, 4), ("p_drop", 36, 4), ("seed", 40, 8), ("params", 48, 8), ("grads", 56, 8), ("adam_m", 64, 8), ("adam_v", 72, 8),
+        ("n_params", 80, 8), ("in_item_id", 88, 8), ("item_id", 96, 8), ("seqlen", 104, 8), ("rows", 112, 8), ("neg_item", 120, 8),
+        ("sample_neg", 128, 4), ("workspace", 136, 8), ("workspace_bytes", 144, 8), ("state", 152, 8), ("lr", 160, 4), ("beta1", 164, 4),
+        ("beta2", 168, 4), ("adam_eps", 172, 4), ("weight_decay", 176, 4), ("perm", 184, 8), ("n_perm", 192, 8), ("perm_stride", 200, 8),
+        ("perm_offset", 208, 8), ("perm_counter", 216, 8), ("loss_log", 224, 8), ("expected_tokens", 232, 4), ("optimizer", 236, 4)]),
+    "FmlpPlan": (224, "dr4sr_fmlp_plan_sizeof", [
+        ("abi_version", 0, 4), ("B", 4, 4), ("L", 8, 4), ("D", 12, 4), ("F", 16, 4), ("n_layer", 20, 4), ("n_items", 24, 4),
+        ("ln_eps", 28, 4), ("p_drop", 32, 4), ("seed", 40, 8), ("params", 48, 8), ("grads", 56, 8), ("adam_m", 64, 8), ("adam_v", 72, 8),
+        ("n_params", 80, 8), ("in_item_id", 88, 8), ("item_id", 96, 8), ("rows", 104, 8), ("neg_item", 112, 8), ("sample_neg", 120, 4),
+        ("workspace", 128, 8), ("workspace_bytes", 136, 8), ("state", 144, 8), ("lr", 152, 4), ("beta1", 156, 4), ("beta2", 160, 4),
+        ("adam_eps", 164, 4), ("weight_decay", 168, 4), ("optimizer", 172, 4), ("perm", 176, 8), ("n_perm", 184, 8),
+        ("perm_stride", 192, 8), ("perm_offset", 200, 8), ("perm_counter", 208, 8), ("loss_log", 216, 8)]),
+    "GruPlan": (224, "dr4sr_gru4rec_plan_sizeof", [
+        ("abi_version", 0, 4), ("B", 4, 4), ("L", 8, 4), ("D", 12, 4), ("H", 16, 4), ("n_layer", 20, 4), ("n_items", 24, 4),
+        ("p_drop", 28, 4), ("seed", 32, 8), ("params", 40, 8), ("grads", 48, 8), ("adam_m", 56, 8), ("adam_v", 64, 8), ("n_params", 72, 8),
+        ("in_item_id", 80, 8), ("item_id", 88, 8), ("seqlen", 96, 8), ("rows", 104, 8), ("neg_item", 112, 8), ("sample_neg", 120, 4),
+        ("workspace", 128, 8), ("workspace_bytes", 136, 8), ("state", 144, 8), ("lr", 152, 4), ("beta1", 156, 4), ("beta2", 160, 4),
+        ("adam_eps", 164, 4), ("weight_decay", 168, 4), ("optimizer", 172, 4), ("perm", 176, 8), ("n_perm", 184, 8),
+        ("perm_stride", 192, 8), ("perm_offset", 200, 8), ("perm_counter", 208, 8), ("loss_log", 216, 8)]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(PLAN_LAYOUTS))
+def test_plan_mirrors_keep_their_field_order_offsets_and_sizes(name):
+    """_lib.py builds the three plan mirrors from shared field blocks: every field sits where the struct of include/dr4sr_hip.h has it
+    (a literal table, not computed from the mirror), and the whole mirror is as large as the compiled struct"""
+    from dr4sr_amd import _lib
+    size, sizeof_sym, table = PLAN_LAYOUTS[name]
+    cls = getattr(_lib, name)
+    got = [(f, getattr(cls, f).offset, getattr(cls, f).size) for f, _ in cls._fields_]
+    assert got == table
+    assert C.sizeof(cls) == size == getattr(_lib.load(), sizeof_sym)()
+    floats = {"ln_eps", "p_drop", "lr", "beta1", "beta2", "adam_eps", "weight_decay"}
+    for f, t in cls._fields_:                       # the types behind the sizes: float fields are floats, seed is unsigned
+        assert (t is C.c_float) == (f in floats), f
+    assert dict(cls._fields_)["seed"] is C.c_uint64 and dict(cls._fields_)["n_params"] is C.c_int64
+
+
 def test_argument_validation_of_the_widening_entry_points():
     """MetaModel / CL4SRec / GRU entry points reject bad arguments before touching the device (ctypes, no GPU needed)"""
     from dr4sr_amd import _lib
