@@ -11,6 +11,8 @@ condition; the decoded sequences, deduplicated, become new training rows of `tra
 backend="hip" runs csrc/regen.hip through the C ABI (dr4sr_regen_encode / dr4sr_regen_decode: all steps of a chunk of rows on the
 device, no host sync per token).  backend="torch" is a batched eager restatement of the same math (padding masks, full prefix
 recompute); it runs on CPU or GPU and is the cross-check of the kernels, not a fall-back: nothing switches to it on its own.
+It lives in regen_torch.py; this module holds the product path: parameters and the two flat buffers, plans, packing, the HIP calls
+and the chunk drivers.
 """
 from __future__ import annotations
 
@@ -21,10 +23,9 @@ import math
 import os
 
 import torch
-import torch.nn.functional as F
 
-from . import _lib, regen_dropout
-from .regen_dropout import RegenDropout
+from . import _lib
+from .regen_dropout import RegenDropout, eval_mode      # RegenDropout: callers import it from here
 
 D, H, FF, N_LAYER, N_POS, MAX_LEN, LN_EPS = 64, 2, 256, 2, 50, 25, 1e-12
 NUM_ITEM = {"toy": 11925, "sport": 18358, "beauty": 12102, "yelp": 20034}     # 3.Hybrid_inference.py:237-242
@@ -62,16 +63,33 @@ def score_param_names():
     return names
 
 
+_ENC_SHAPES = [(3 * D, D), (3 * D,), (D, D), (D,), (FF, D), (FF,), (D, FF), (D,), (D,), (D,), (D,), (D,)]      # the shapes of _ENC
+
+
 def score_param_shapes(n_rows: int, K: int):
-    enc = [(3 * D, D), (3 * D,), (D, D), (D,), (FF, D), (FF,), (D, FF), (D,), (D,), (D,), (D,), (D,)]
-    return param_shapes(n_rows, K) + enc * N_LAYER + [(D, D), (D,), (K, D), (K,)]
+    return param_shapes(n_rows, K) + _ENC_SHAPES * N_LAYER + [(D, D), (D,), (K, D), (K,)]
 
 
 def param_shapes(n_rows: int, K: int):
-    enc = [(3 * D, D), (3 * D,), (D, D), (D,), (FF, D), (FF,), (D, FF), (D,), (D,), (D,), (D,), (D,)]
     dec = [(3 * D, D), (3 * D,), (D, D), (D,), (3 * D, D), (3 * D,), (D, D), (D,), (FF, D), (FF,), (D, FF), (D,)] + [(D,)] * 6
-    return ([(n_rows, D), (N_POS, D)] + enc * N_LAYER + [(D,), (D,)] + dec * N_LAYER + [(D,), (D,)]
+    return ([(n_rows, D), (N_POS, D)] + _ENC_SHAPES * N_LAYER + [(D,), (D,)] + dec * N_LAYER + [(D,), (D,)]
             + [(K * D, D), (K * D,), (K * D, K * D), (K * D,)])
+
+
+def _chunks(n: int, size: int):
+    """(a, b) of the chunks [a, b) of at most `size` rows that cover range(n); none for n = 0"""
+    return ((a, min(n, a + size)) for a in range(0, n, size))
+
+
+def _check_backend(backend):
+    if backend not in ("hip", "torch"):
+        raise ValueError(f"backend must be 'hip' or 'torch', not {backend!r}")
+
+
+def _torch():
+    """the eager restatement, for the backend="torch" branches (regen_torch.py imports this module, so it is imported at first use)"""
+    from . import regen_torch
+    return regen_torch
 
 
 class RegenModel:
@@ -85,9 +103,9 @@ class RegenModel:
         self.p = {k: v.to(self.device, torch.float32).contiguous() for k, v in params.items()}
         self._flat = None
         self._score_flat = None
+        self._layouts = {}
         self._cast = {}
         self.has_condition_encoder = "condition_encoder.condition_layer.2.weight" in self.p
-        self.record_gaps = None        # a list: the torch restatement appends (gap, top) [rows, 24] per batch it decodes
 
     @classmethod
     def from_state_dict(cls, sd: dict, device="cuda", dataset: str | None = None):
@@ -120,51 +138,58 @@ class RegenModel:
         return cls(params, n_rows, K, device)
 
     # ------------------------------------------------------------------------------------------------ HIP
+    def _layout(self, score: bool):
+        """(element count, offsets, names) of dr4sr_regen_param_layout's 70 tensors or, score=True, of the 98 tensors of
+        dr4sr_regen_score_param_layout; asked of the library once"""
+        if score not in self._layouts:
+            fn, names = ("dr4sr_regen_score_param_layout", score_param_names()) if score else ("dr4sr_regen_param_layout", param_names())
+            off = (C.c_int64 * len(names))()
+            n = getattr(_lib.load(), fn)(self.n_rows, self.K, off)
+            if n < 0:
+                _lib.check(int(n), fn)
+            self._layouts[score] = int(n), list(off), names
+        return self._layouts[score]
+
+    def _fill_flat(self, buf, score: bool, only=None):
+        """write the named parameters (`only`: those names) into a flat buffer of the 70- or the 98-tensor layout"""
+        _, off, names = self._layout(score)
+        for o, name in zip(off, names):
+            if (only is None or name in only) and (name in self.p or not score):      # only the score layout's condition_encoder.* may be absent
+                buf[o:o + self.p[name].numel()] = self.p[name].reshape(-1)
+        return buf
+
     def flat(self):
         """the flat fp32 parameter buffer of dr4sr_regen_param_layout"""
         if self._flat is None:
-            lib = _lib.load()
-            off = (C.c_int64 * _lib.REGEN_TENSORS)()
-            n = lib.dr4sr_regen_param_layout(self.n_rows, self.K, off)
-            if n < 0:
-                _lib.check(int(n), "dr4sr_regen_param_layout")
-            buf = torch.empty(int(n), dtype=torch.float32, device=self.device)
-            for i, name in enumerate(param_names()):
-                t = self.p[name].reshape(-1)
-                buf[off[i]:off[i] + t.numel()] = t
-            self._flat = buf
+            self._flat = self._fill_flat(torch.zeros(self._layout(False)[0], dtype=torch.float32, device=self.device), False)
         return self._flat
 
     def score_flat(self):
         """the flat fp32 parameter buffer of dr4sr_regen_score_param_layout (condition_encoder.* zero when the model has none)"""
         if self._score_flat is None:
-            lib = _lib.load()
-            off = (C.c_int64 * _lib.REGEN_SCORE_TENSORS)()
-            n = lib.dr4sr_regen_score_param_layout(self.n_rows, self.K, off)
-            if n < 0:
-                _lib.check(int(n), "dr4sr_regen_score_param_layout")
-            buf = torch.zeros(int(n), dtype=torch.float32, device=self.device)
-            for i, name in enumerate(score_param_names()):
-                if name in self.p:
-                    t = self.p[name].reshape(-1)
-                    buf[off[i]:off[i] + t.numel()] = t
-            self._score_flat = buf
+            self._score_flat = self._fill_flat(torch.zeros(self._layout(True)[0], dtype=torch.float32, device=self.device), True)
         return self._score_flat
 
-    def score_plan(self):
-        p = self.plan()
-        flat = self.score_flat()
-        p.params = flat.data_ptr()
-        p.n_params = flat.numel()
-        return p
+    def adopt_score_flat(self, buf):
+        """make `buf` the model's score buffer (a trainer's padded master holds it as a view): score_plan() points at it from now on.
+        Its contents are the caller's business; it must be a contiguous fp32 tensor of score_flat()'s length on the model's device"""
+        n = self._layout(True)[0]
+        same_device = buf.device.type == self.device.type and self.device.index in (None, buf.device.index)
+        if buf.numel() != n or buf.dim() != 1 or buf.dtype != torch.float32 or not same_device or not buf.is_contiguous():
+            raise ValueError(f"the score buffer must hold {n} contiguous fp32 values on {self.device}")
+        self._score_flat = buf
 
-    def plan(self):
+    def score_plan(self):
+        return self.plan(self.score_flat())
+
+    def plan(self, flat=None):
+        """the plan over flat(), or over the given parameter buffer (score_plan: the 98-tensor one)"""
         p = _lib.RegenPlan()
         p.abi_version = _lib.ABI_VERSION
         p.n_rows, p.K, p.max_len = self.n_rows, self.K, MAX_LEN
         p.D, p.H, p.F, p.n_layer = D, H, FF, N_LAYER
         p.ln_eps = LN_EPS
-        flat = self.flat()
+        flat = self.flat() if flat is None else flat
         p.params = flat.data_ptr()
         p.n_params = flat.numel()
         return p
@@ -203,153 +228,40 @@ class RegenModel:
                                           C.c_void_p(ws.data_ptr()), int(nb), _lib.ptr(tok), _lib.ptr(ln), st), "dr4sr_regen_decode")
         return tok.cpu(), ln.cpu()
 
-    # ------------------------------------------------------------------------------------------------ torch restatement
-    def _mha(self, pre, xq, xkv, key_bias):
-        W, b = self.p[pre + ".in_proj_weight"], self.p[pre + ".in_proj_bias"]
-        B, Lq, _ = xq.shape
-        Lk = xkv.shape[1]
-        q = F.linear(xq, W[:D], b[:D]).view(B, Lq, H, D // H).transpose(1, 2)
-        k = F.linear(xkv, W[D:2 * D], b[D:2 * D]).view(B, Lk, H, D // H).transpose(1, 2)
-        v = F.linear(xkv, W[2 * D:], b[2 * D:]).view(B, Lk, H, D // H).transpose(1, 2)
-        s = (q @ k.transpose(-1, -2)) / math.sqrt(D // H) + key_bias
-        o = (torch.softmax(s, -1) @ v).transpose(1, 2).reshape(B, Lq, D)
-        return F.linear(o, self.p[pre + ".out_proj.weight"], self.p[pre + ".out_proj.bias"])
-
-    def _ln(self, x, pre):
-        return F.layer_norm(x, (D,), self.p[pre + ".weight"], self.p[pre + ".bias"], LN_EPS)
-
-    def _ffn(self, x, pre):
-        h = F.gelu(F.linear(x, self.p[pre + ".linear1.weight"], self.p[pre + ".linear1.bias"]))
-        return F.linear(h, self.p[pre + ".linear2.weight"], self.p[pre + ".linear2.bias"])
-
-    def _encode_torch(self, src, lens):
-        """encoder (no attention mask in the reference; key padding here only hides the batch's padding) + encoder.norm"""
-        E, P = self.p["item_embedding.weight"], self.p["position_embedding.weight"]
-        Ls = src.shape[1]
-        x = E[src] + P[:Ls]
-        pad = torch.arange(Ls, device=src.device)[None, :] >= lens[:, None]
-        kb = torch.zeros(pad.shape, device=src.device).masked_fill(pad, float("-inf"))[:, None, None, :]
-        for i in range(N_LAYER):
-            pre = f"transformer.encoder.layers.{i}"
-            x = self._ln(x + self._mha(pre + ".self_attn", x, x, kb), pre + ".norm1")
-            x = self._ln(x + self._ffn(x, pre), pre + ".norm2")
-        return self._ln(x, "transformer.encoder.norm"), kb
-
-    def _decode_torch(self, src, lens, cond0, n_cond, rows_per_batch=ROWS_PER_TORCH):
-        src, lens = src.to(self.device), lens.to(self.device)
-        S = src.shape[0]
-        mem0, kb0 = self._encode_torch(src, lens)
-        c1 = torch.relu(F.linear(mem0, self.p["condition_linear.0.weight"], self.p["condition_linear.0.bias"]))
-        W2, b2 = self.p["condition_linear.2.weight"], self.p["condition_linear.2.bias"]
-        toks, lns = [], []
-        for c in range(n_cond):
-            k = cond0 + c
-            mem = F.linear(c1, W2[k * D:(k + 1) * D], b2[k * D:(k + 1) * D])       # features k*64:(k+1)*64 (3.Hybrid_inference.py:146)
-            for a in range(0, S, rows_per_batch):
-                g = None
-                if self.record_gaps is not None:
-                    m = min(S, a + rows_per_batch) - a
-                    g = (torch.full((m, MAX_LEN - 1), float("nan"), device=self.device), torch.full((m, MAX_LEN - 1), float("nan"), device=self.device))
-                    self.record_gaps.append(g)
-                t, n = self._greedy_torch(src[a:a + rows_per_batch], mem[a:a + rows_per_batch], kb0[a:a + rows_per_batch], g)
-                toks.append(t)
-                lns.append(n)
-        return torch.cat(toks).cpu(), torch.cat(lns).cpu()
-
-    def _greedy_torch(self, src, mem, kb, gaps=None):
-        """greedy_decode (3.Hybrid_inference.py:185-208) over a batch of rows, recomputing the whole prefix at each step"""
-        E, P = self.p["item_embedding.weight"], self.p["position_embedding.weight"]
-        R = src.shape[0]
-        ys = torch.full((R, 1), self.sos, dtype=torch.int64, device=self.device)
-        alive = torch.ones(R, dtype=torch.bool, device=self.device)
-        n = torch.ones(R, dtype=torch.int32, device=self.device)
-        for i in range(MAX_LEN - 1):
-            idx = alive.nonzero().squeeze(1)
-            if idx.numel() == 0:
-                break
-            y = ys[idx]
-            T = y.shape[1]
-            x = E[y] + P[:T]
-            causal = torch.full((T, T), float("-inf"), device=self.device).triu(1)
-            for l in range(N_LAYER):
-                pre = f"transformer.decoder.layers.{l}"
-                x = self._ln(x + self._mha(pre + ".self_attn", x, x, causal), pre + ".norm1")
-                x = self._ln(x + self._mha(pre + ".multihead_attn", x, mem[idx], kb[idx]), pre + ".norm2")
-                x = self._ln(x + self._ffn(x, pre), pre + ".norm3")
-            h = self._ln(x[:, -1], "transformer.decoder.norm")
-            logits = h @ E.T
-            if i <= 1:      # inference_mask: ids of src (the padding repeats SOS, which is in ys) and not in ys
-                allowed = torch.zeros_like(logits, dtype=torch.bool).scatter(-1, src[idx], True)
-            else:           # inference_mask_generative
-                allowed = torch.ones_like(logits, dtype=torch.bool)
-            allowed = allowed.scatter(-1, y, False)
-            masked = logits.masked_fill(~allowed, float("-inf"))
-            nxt = masked.argmax(-1)
-            if gaps is not None:     # best - second-best allowed logit, and the best (the cross-checks' tie rule)
-                v = torch.topk(masked, 2, dim=-1).values
-                gaps[0][idx, i] = v[:, 0] - v[:, 1]
-                gaps[1][idx, i] = v[:, 0]
-            col = torch.zeros(R, dtype=torch.int64, device=self.device)
-            col[idx] = nxt
-            ys = torch.cat([ys, col[:, None]], 1)
-            n[idx] += 1
-            alive[idx] = nxt != self.eos
-        out = torch.zeros(R, MAX_LEN, dtype=torch.int64, device=self.device)
-        out[:, :ys.shape[1]] = ys
-        out[torch.arange(MAX_LEN, device=self.device)[None, :] >= n[:, None].long()] = 0
-        return out, n
-
     # ------------------------------------------------------------------------------------------------ public
     @torch.no_grad()
     def decode(self, src_list, cond0: int = 0, n_cond: int | None = None, backend: str = "hip"):
         """greedy decode of every source under conditions cond0 .. cond0 + n_cond - 1: a list (condition-major, as the reference
         appends them) of token lists [SOS, ..., EOS or the 24th item]"""
+        return self._decode_chunks(src_list, cond0, n_cond, backend)[0]
+
+    def _decode_chunks(self, src_list, cond0, n_cond, backend, gaps=False):
+        """decode()'s chunk driver: (token lists,), or with gaps (backend="torch" only) (token lists, gap, top): regen_torch.decode's
+        record, [n_cond * S, MAX_LEN - 1] each, in the order of the token lists"""
         n_cond = self.K - cond0 if n_cond is None else int(n_cond)
         if not (0 <= cond0 and n_cond >= 1 and cond0 + n_cond <= self.K):
             raise ValueError(f"conditions {cond0}..{cond0 + n_cond - 1} outside 0..{self.K - 1}")
-        if backend not in ("hip", "torch"):
-            raise ValueError(f"backend must be 'hip' or 'torch', not {backend!r}")
+        _check_backend(backend)
         src, lens = self._pack(src_list)
         S = src.shape[0]
         per = {c: [None] * S for c in range(n_cond)}
-        chunk = max(1, ROWS_PER_CALL // n_cond) if backend == "hip" else max(1, 4 * ROWS_PER_TORCH)
-        for a in range(0, S, chunk):
-            b = min(S, a + chunk)
+        record = tuple(torch.empty(n_cond, S, MAX_LEN - 1) for _ in range(2)) if gaps else ()
+        for a, b in _chunks(S, max(1, ROWS_PER_CALL // n_cond) if backend == "hip" else 4 * ROWS_PER_TORCH):
             Lc = int(lens[a:b].max())
-            fn = self._decode_hip if backend == "hip" else self._decode_torch
-            tok, ln = fn(src[a:b, :Lc].contiguous(), lens[a:b].contiguous(), cond0, n_cond)
+            chunk = src[a:b, :Lc].contiguous(), lens[a:b].contiguous(), cond0, n_cond
+            tok, ln = self._decode_hip(*chunk) if backend == "hip" else _torch().decode(self, *chunk, record=tuple(r[:, a:b] for r in record))
             tl, nl = tok.tolist(), ln.tolist()
             for c in range(n_cond):
                 for j in range(b - a):
                     r = c * (b - a) + j
                     per[c][a + j] = tl[r][:nl[r]]
-        return [per[c][s] for c in range(n_cond) for s in range(S)]
+        return ([per[c][s] for c in range(n_cond) for s in range(S)], *(r.flatten(0, 1) for r in record))
 
     @torch.no_grad()
     def decode_with_gaps(self, src_list, cond0: int = 0, n_cond: int | None = None):
         """backend="torch" decode that also returns, per row (same order) and step, the gap between the best and the second-best
         ALLOWED logit and the best logit (NaN after the row ended): a step whose gap is within rounding may legitimately differ"""
-        n_cond = self.K - cond0 if n_cond is None else int(n_cond)
-        self.record_gaps = []
-        try:
-            src, lens = self._pack(src_list)
-            S = src.shape[0]
-            toks = self.decode(src_list, cond0, n_cond, "torch")
-            chunk = max(1, 4 * ROWS_PER_TORCH)
-            gap = torch.empty(n_cond * S, MAX_LEN - 1)
-            top = torch.empty(n_cond * S, MAX_LEN - 1)
-            it = iter(self.record_gaps)
-            for a in range(0, S, chunk):
-                b = min(S, a + chunk)
-                for c in range(n_cond):
-                    for a2 in range(a, b, ROWS_PER_TORCH):
-                        g, t = next(it)
-                        m = g.shape[0]
-                        gap[c * S + a2:c * S + a2 + m] = g.cpu()
-                        top[c * S + a2:c * S + a2 + m] = t.cpu()
-        finally:
-            self.record_gaps = None
-        return toks, gap, top
+        return self._decode_chunks(src_list, cond0, n_cond, "torch", gaps=True)
 
     def translate(self, src_list, condition: int, backend: str = "hip"):
         """the reference's translate(model, src) under set_condition(condition), for every source: one int64 tensor each"""
@@ -388,132 +300,51 @@ class RegenModel:
             self._cast[key] = {k: v.to(device=device, dtype=dtype) for k, v in self.p.items()}
         return self._cast[key]
 
-    def _score_torch(self, src, tgt, tgt_len, w, want_cond, causal_source, dtype, params=None, drop=None):
-        """Generator.forward + cross_entropy(reduction='none') of 2.Pretrain_regenerator.py, batched, from the named parameters:
-        (nll [n_w, n, T] or None when w is None, condition logits [n, K] or None).  `params` (name -> tensor of `dtype` on src's
-        device) replaces the model's own: loss_and_grad passes leaves that require grad.  drop=None is eval mode; a _TorchDrop is
-        train mode: the kernels' own masks (regen_dropout.py) at nn.Transformer's 30 dropout sites"""
-        dev = src.device
-        p = self._params_as(dtype, dev) if params is None else params
-        E, P = p["item_embedding.weight"], p["position_embedding.weight"]
-        n, Ls = src.shape
-        T = tgt.shape[1] - 1
-        tgt_in, tgt_out = tgt[:, :-1], tgt[:, 1:]
-        ninf = float("-inf")
-
-        nodrop = drop is None
-        rows_ = (lambda x, s: x) if nodrop else (lambda x, s: x * drop.rows(s, x))
-        probs_ = (lambda a, s: a) if nodrop else (lambda a, s: a * drop.probs(s, a))
-
-        def mha(pre, xq, xkv, bias, st, l, kind):
-            W, b = p[pre + ".in_proj_weight"], p[pre + ".in_proj_bias"]
-            B, Lq, _ = xq.shape
-            Lk = xkv.shape[1]
-            q = F.linear(xq, W[:D], b[:D]).view(B, Lq, H, D // H).transpose(1, 2)
-            k = F.linear(xkv, W[D:2 * D], b[D:2 * D]).view(B, Lk, H, D // H).transpose(1, 2)
-            v = F.linear(xkv, W[2 * D:], b[2 * D:]).view(B, Lk, H, D // H).transpose(1, 2)
-            a = probs_(torch.softmax((q @ k.transpose(-1, -2)) / math.sqrt(D // H) + bias, -1), (st, l, kind))
-            return rows_(F.linear((a @ v).transpose(1, 2).reshape(B, Lq, D), p[pre + ".out_proj.weight"], p[pre + ".out_proj.bias"]),
-                         (st, l, kind + 1))
-
-        def ln(x, pre):
-            return F.layer_norm(x, (D,), p[pre + ".weight"], p[pre + ".bias"], LN_EPS)
-
-        def ffn(x, pre, st, l, kind):
-            hid = rows_(F.gelu(F.linear(x, p[pre + ".linear1.weight"], p[pre + ".linear1.bias"])), (st, l, kind))
-            return rows_(F.linear(hid, p[pre + ".linear2.weight"], p[pre + ".linear2.bias"]), (st, l, kind + 1))
-
-        def enc_layers(x, bias, stem, st):
-            for i in range(N_LAYER):
-                pre = f"{stem}.layers.{i}"
-                x = ln(x + mha(pre + ".self_attn", x, x, bias, st, i, 0), pre + ".norm1")
-                x = ln(x + ffn(x, pre, st, i, 2), pre + ".norm2")
-            return x
-
-        def key_bias(ids):
-            return torch.zeros(ids.shape, dtype=dtype, device=dev).masked_fill(ids == 0, ninf)[:, None, None, :]
-
-        def causal(L):
-            return torch.full((L, L), ninf, dtype=dtype, device=dev).triu(1)
-
-        tgt_kb = key_bias(tgt_in)
-        x_t = rows_(E[tgt_in] + P[:T], "tgt_emb")
-        cond = None
-        if want_cond:
-            y = enc_layers(x_t, causal(T) + tgt_kb, "condition_encoder.encoder", regen_dropout.STACK_COND)
-            keep = torch.arange(T, device=dev)[None, :] < tgt_len[:, None]
-            pooled = (y * keep[:, :, None].to(dtype)).sum(1) / tgt_len[:, None].to(dtype)
-            hid = torch.relu(F.linear(pooled, p["condition_encoder.condition_layer.0.weight"], p["condition_encoder.condition_layer.0.bias"]))
-            cond = F.linear(hid, p["condition_encoder.condition_layer.2.weight"], p["condition_encoder.condition_layer.2.bias"])
-        if w is None:
-            return None, cond
-        src_kb = key_bias(src)
-        x = enc_layers(rows_(E[src] + P[:Ls], "src_emb"), (causal(Ls) if causal_source else 0) + src_kb, "transformer.encoder",
-                       regen_dropout.STACK_SRC)
-        mem = ln(x, "transformer.encoder.norm")
-        c1 = torch.relu(F.linear(mem, p["condition_linear.0.weight"], p["condition_linear.0.bias"]))
-        mem = F.linear(c1, p["condition_linear.2.weight"], p["condition_linear.2.bias"]).view(n, Ls, self.K, D)
-        dup = ((src[:, :, None] == src[:, None, :]) & torch.ones(Ls, Ls, dtype=torch.bool, device=dev).tril(-1)).any(-1)   # id seen earlier
-        Es = E[src]                                                           # the only table rows the masked logits keep
-        hit = (tgt_out[:, :, None] == src[:, None, :]) & ~dup[:, None, :]     # [n, T, Ls]: the slot of the target id, if any
-        dec_bias = causal(T) + tgt_kb
-        out = []
-        for wi in w.to(device=dev, dtype=dtype):
-            mc = (mem * wi[:, None, :, None]).sum(-2)
-            h = x_t
-            for i in range(N_LAYER):
-                pre = f"transformer.decoder.layers.{i}"
-                h = ln(h + mha(pre + ".self_attn", h, h, dec_bias, regen_dropout.STACK_DEC, i, 0), pre + ".norm1")
-                h = ln(h + mha(pre + ".multihead_attn", h, mc, src_kb, regen_dropout.STACK_DEC, i, 2), pre + ".norm2")
-                h = ln(h + ffn(h, pre, regen_dropout.STACK_DEC, i, 4), pre + ".norm3")
-            h = ln(h, "transformer.decoder.norm")
-            lg = (h @ Es.transpose(1, 2)).masked_fill(dup[:, None, :], ninf)
-            lse = torch.logsumexp(lg, -1)
-            tl = torch.where(hit, lg, torch.zeros((), dtype=dtype, device=dev)).sum(-1)
-            nll = torch.where(hit.any(-1), lse - tl, torch.full((), float("inf"), dtype=dtype, device=dev))
-            out.append(nll.masked_fill(tgt_out == 0, 0.0))
-        return torch.stack(out), cond
+    def _hip(self, name, ws_query, ws_sizes, pre, post, workspace, dropout, pair0, *, backward=False, grad=None, accumulate=False):
+        """One call of the scoring family, enqueued on the current stream: name(plan, *pre, workspace, its bytes, *post, stream) in eval
+        mode, name_train(..., p, seed, step, pair0, stream) with a RegenDropout.  Tensors in pre / post go in as their pointers.  The
+        workspace is checked against ws_query(plan, *ws_sizes) by the library and allocated here when None.  A backward call
+        (backward=True) also takes `grad` and `accumulate`: the flat gradient, a new buffer when None, goes in front of `post` and
+        `accumulate` behind it, and the buffer is returned"""
+        lib = _lib.load()
+        plan = self.score_plan()
+        nb = getattr(lib, ws_query)(C.byref(plan), *ws_sizes)
+        if nb < 0:
+            _lib.check(int(nb), ws_query)
+        if workspace is None:
+            workspace = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
+        if backward:
+            if grad is None:
+                if accumulate:
+                    raise ValueError("accumulate=True needs the gradient buffer to add to")
+                grad = torch.empty(plan.n_params, dtype=torch.float32, device=self.device)
+            if grad.numel() != plan.n_params or grad.dtype != torch.float32:
+                raise ValueError(f"grad must hold {plan.n_params} fp32 values")
+            post = (grad, *post, int(bool(accumulate)))
+        args = [_lib.ptr(v) if isinstance(v, torch.Tensor) else v
+                for v in (C.byref(plan), *pre, C.c_void_p(workspace.data_ptr()), workspace.numel(), *post)]
+        if eval_mode(dropout):
+            _lib.check(getattr(lib, name)(*args, _lib.cur_stream()), name)
+        else:
+            _lib.check(getattr(lib, name + "_train")(*args, *_drop_args(dropout, pair0), _lib.cur_stream()), name + "_train")
+        return grad
 
     def score_device(self, src, src_len, tgt, tgt_len, w, causal_source=True, workspace=None, dropout=None, pair0=0):
         """the HIP call on device tensors (src [n, Ls], tgt [n, T + 1] int64, w [n_w, n, K] fp32): nll [n_w, n, T] on the device.
         Only enqueues on the current stream (capturable); `workspace` may be reused between calls of the same sizes.  dropout (a
         RegenDropout) scores in train mode; row i then takes the masks of global pair pair0 + i"""
-        lib = _lib.load()
-        plan = self.score_plan()
-        n, Ls = src.shape
-        T = tgt.shape[1] - 1
-        n_w = w.shape[0]
-        nb = lib.dr4sr_regen_score_workspace_bytes(C.byref(plan), n, Ls, T, n_w)
-        if nb < 0:
-            _lib.check(int(nb), "dr4sr_regen_score_workspace_bytes")
-        if workspace is None:
-            workspace = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
+        (n, Ls), T, n_w = src.shape, tgt.shape[1] - 1, w.shape[0]
         nll = torch.empty(n_w, n, T, dtype=torch.float32, device=self.device)
-        args = (C.byref(plan), _lib.ptr(src), _lib.ptr(src_len), _lib.ptr(tgt), _lib.ptr(tgt_len), n, Ls, T, _lib.ptr(w), n_w,
-                int(bool(causal_source)), C.c_void_p(workspace.data_ptr()), workspace.numel(), _lib.ptr(nll))
-        if _eval_mode(dropout):
-            _lib.check(lib.dr4sr_regen_score(*args, _lib.cur_stream()), "dr4sr_regen_score")
-        else:
-            _lib.check(lib.dr4sr_regen_score_train(*args, *_drop_args(dropout, pair0), _lib.cur_stream()), "dr4sr_regen_score_train")
+        self._hip("dr4sr_regen_score", "dr4sr_regen_score_workspace_bytes", (n, Ls, T, n_w),
+                  (src, src_len, tgt, tgt_len, n, Ls, T, w, n_w, int(bool(causal_source))), (nll,), workspace, dropout, pair0)
         return nll
 
     def condition_device(self, tgt, tgt_len, workspace=None, dropout=None, pair0=0):
         """condition logits [n, K] of the condition_encoder on device tensors (HIP; only enqueues); dropout / pair0 as score_device"""
-        lib = _lib.load()
-        plan = self.score_plan()
         n, T = tgt.shape[0], tgt.shape[1] - 1
-        nb = lib.dr4sr_regen_score_workspace_bytes(C.byref(plan), n, 1, T, 1)
-        if nb < 0:
-            _lib.check(int(nb), "dr4sr_regen_score_workspace_bytes")
-        if workspace is None:
-            workspace = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
         out = torch.empty(n, self.K, dtype=torch.float32, device=self.device)
-        args = (C.byref(plan), _lib.ptr(tgt), _lib.ptr(tgt_len), n, T, C.c_void_p(workspace.data_ptr()), workspace.numel(), _lib.ptr(out))
-        if _eval_mode(dropout):
-            _lib.check(lib.dr4sr_regen_score_condition(*args, _lib.cur_stream()), "dr4sr_regen_score_condition")
-        else:
-            _lib.check(lib.dr4sr_regen_score_condition_train(*args, *_drop_args(dropout, pair0), _lib.cur_stream()),
-                       "dr4sr_regen_score_condition_train")
+        self._hip("dr4sr_regen_score_condition", "dr4sr_regen_score_workspace_bytes", (n, 1, T, 1), (tgt, tgt_len, n, T), (out,),
+                  workspace, dropout, pair0)
         return out
 
     # ------------------------------------------------------------------------------------------------ parameters in and out
@@ -528,99 +359,48 @@ class RegenModel:
     def load_params(self, params: dict):
         """overwrite parameters IN PLACE: self.p, the dtype casts and both flat buffers keep their device addresses, so plans, views
         and captured graphs stay valid.  `params` maps state-dict names to tensors of the stored shapes (a subset is allowed)"""
+        params = {k: v for k, v in params.items() if k != "item_embedding_decoder.weight"}      # the same table as item_embedding.weight
         for name, v in params.items():
-            if name == "item_embedding_decoder.weight":
-                continue
             if name not in self.p:
                 raise KeyError(f"{name} is not a parameter of this model")
             if tuple(v.shape) != tuple(self.p[name].shape):
                 raise ValueError(f"{name}: shape {tuple(v.shape)}, expected {tuple(self.p[name].shape)}")
         for name, v in params.items():
-            if name == "item_embedding_decoder.weight":
-                continue
             self.p[name].copy_(v.detach().to(self.device, torch.float32))
             for cast in self._cast.values():
                 cast[name].copy_(self.p[name].to(device=cast[name].device, dtype=cast[name].dtype))
-        for buf, names, fn, cnt in ((self._flat, param_names(), "dr4sr_regen_param_layout", _lib.REGEN_TENSORS),
-                                    (self._score_flat, score_param_names(), "dr4sr_regen_score_param_layout", _lib.REGEN_SCORE_TENSORS)):
-            if buf is None:
-                continue
-            off = (C.c_int64 * cnt)()
-            getattr(_lib.load(), fn)(self.n_rows, self.K, off)
-            for i, name in enumerate(names):
-                if name in params:
-                    buf[off[i]:off[i] + self.p[name].numel()] = self.p[name].reshape(-1)
+        for buf, score in ((self._flat, False), (self._score_flat, True)):
+            if buf is not None:
+                self._fill_flat(buf, score, params)
 
     # ------------------------------------------------------------------------------------------------ gradients
     def grads_from_flat(self, flat):
         """views of a flat gradient buffer in the 98-tensor score layout, by state-dict name (70 names without a condition encoder)"""
-        off = (C.c_int64 * _lib.REGEN_SCORE_TENSORS)()
-        _lib.load().dr4sr_regen_score_param_layout(self.n_rows, self.K, off)
-        out = {}
-        for i, (name, shape) in enumerate(zip(score_param_names(), score_param_shapes(self.n_rows, self.K))):
-            if name in self.p:
-                out[name] = flat[off[i]:off[i] + math.prod(shape)].view(shape)
-        return out
+        _, off, names = self._layout(True)
+        return {name: flat[o:o + math.prod(shape)].view(shape)
+                for o, name, shape in zip(off, names, score_param_shapes(self.n_rows, self.K)) if name in self.p}
 
     def condition_bwd_device(self, tgt, tgt_len, dlogits, grad=None, accumulate=False, workspace=None, dropout=None, pair0=0):
         """the HIP backward of condition_device on device tensors: dlogits [n, K] fp32 -> the flat gradient (98-tensor score layout;
         condition_encoder.* and the two tables receive values).  accumulate=False overwrites every element of `grad` (a new buffer
         when None), True adds to it.  Only enqueues on the current stream (capturable); the same inputs give the same bits"""
-        lib = _lib.load()
-        plan = self.score_plan()
         n, T = tgt.shape[0], tgt.shape[1] - 1
-        nb = lib.dr4sr_regen_score_condition_bwd_workspace_bytes(C.byref(plan), n, T)
-        if nb < 0:
-            _lib.check(int(nb), "dr4sr_regen_score_condition_bwd_workspace_bytes")
-        if workspace is None:
-            workspace = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
-        if grad is None:
-            if accumulate:
-                raise ValueError("accumulate=True needs the gradient buffer to add to")
-            grad = torch.empty(plan.n_params, dtype=torch.float32, device=self.device)
-        if grad.numel() != plan.n_params or grad.dtype != torch.float32:
-            raise ValueError(f"grad must hold {plan.n_params} fp32 values")
-        args = (C.byref(plan), _lib.ptr(tgt), _lib.ptr(tgt_len), n, T, _lib.ptr(dlogits), C.c_void_p(workspace.data_ptr()), workspace.numel(),
-                _lib.ptr(grad), int(bool(accumulate)))
-        if _eval_mode(dropout):
-            _lib.check(lib.dr4sr_regen_score_condition_bwd(*args, _lib.cur_stream()), "dr4sr_regen_score_condition_bwd")
-        else:
-            _lib.check(lib.dr4sr_regen_score_condition_bwd_train(*args, *_drop_args(dropout, pair0), _lib.cur_stream()),
-                       "dr4sr_regen_score_condition_bwd_train")
-        return grad
+        return self._hip("dr4sr_regen_score_condition_bwd", "dr4sr_regen_score_condition_bwd_workspace_bytes", (n, T),
+                         (tgt, tgt_len, n, T, dlogits), (), workspace, dropout, pair0, backward=True, grad=grad, accumulate=accumulate)
 
     def score_bwd_device(self, src, src_len, tgt, tgt_len, w, dnll, causal_source=True, grad=None, accumulate=False, workspace=None,
                          dropout=None, pair0=0):
         """the HIP backward of score_device on device tensors: dnll [n_w, n, T] fp32 -> (flat gradient in the 98-tensor score layout,
         dw [n_w, n, K], nll [n_w, n, T]).  Self-contained (runs the forward it needs); accumulate=False overwrites every element of
         `grad` (a new buffer when None), True adds.  Only enqueues on the current stream; the same inputs give the same bits"""
-        lib = _lib.load()
-        plan = self.score_plan()
-        n, Ls = src.shape
-        T = tgt.shape[1] - 1
-        n_w = w.shape[0]
-        nb = lib.dr4sr_regen_score_bwd_workspace_bytes(C.byref(plan), n, Ls, T, n_w)
-        if nb < 0:
-            _lib.check(int(nb), "dr4sr_regen_score_bwd_workspace_bytes")
-        if workspace is None:
-            workspace = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
-        if grad is None:
-            if accumulate:
-                raise ValueError("accumulate=True needs the gradient buffer to add to")
-            grad = torch.empty(plan.n_params, dtype=torch.float32, device=self.device)
-        if grad.numel() != plan.n_params or grad.dtype != torch.float32:
-            raise ValueError(f"grad must hold {plan.n_params} fp32 values")
+        (n, Ls), T, n_w = src.shape, tgt.shape[1] - 1, w.shape[0]
         if tuple(dnll.shape) != (n_w, n, T):
             raise ValueError(f"dnll of shape {tuple(dnll.shape)}, expected ({n_w}, {n}, {T})")
         dw = torch.empty(n_w, n, self.K, dtype=torch.float32, device=self.device)
         nll = torch.empty(n_w, n, T, dtype=torch.float32, device=self.device)
-        args = (C.byref(plan), _lib.ptr(src), _lib.ptr(src_len), _lib.ptr(tgt), _lib.ptr(tgt_len), n, Ls, T, _lib.ptr(w), n_w,
-                int(bool(causal_source)), _lib.ptr(dnll), C.c_void_p(workspace.data_ptr()), workspace.numel(), _lib.ptr(grad), _lib.ptr(dw),
-                _lib.ptr(nll), int(bool(accumulate)))
-        if _eval_mode(dropout):
-            _lib.check(lib.dr4sr_regen_score_bwd(*args, _lib.cur_stream()), "dr4sr_regen_score_bwd")
-        else:
-            _lib.check(lib.dr4sr_regen_score_bwd_train(*args, *_drop_args(dropout, pair0), _lib.cur_stream()), "dr4sr_regen_score_bwd_train")
+        grad = self._hip("dr4sr_regen_score_bwd", "dr4sr_regen_score_bwd_workspace_bytes", (n, Ls, T, n_w),
+                         (src, src_len, tgt, tgt_len, n, Ls, T, w, n_w, int(bool(causal_source)), dnll), (dw, nll), workspace, dropout,
+                         pair0, backward=True, grad=grad, accumulate=accumulate)
         return grad, dw, nll
 
     def _loss_and_grad_hip(self, src, src_len, tgt, tgt_len, T, conditions, causal_source, noise, tau, entropy_weight, dropout=None, pair0=0):
@@ -632,8 +412,7 @@ class RegenModel:
         loss = torch.zeros((), dtype=torch.float64)
         entropy = torch.zeros((), dtype=torch.float64)
         dws, conds = [], []
-        for a in range(0, n, SCORE_BWD_PAIRS_PER_CALL):
-            b = min(n, a + SCORE_BWD_PAIRS_PER_CALL)
+        for a, b in _chunks(n, SCORE_BWD_PAIRS_PER_CALL):
             s_d, sl_d = src[a:b].to(dev).contiguous(), src_len[a:b].to(dev).contiguous()
             t_d, tl_d = tgt[a:b].to(dev).contiguous(), tgt_len[a:b].to(dev).contiguous()
             c = self.condition_device(t_d, tl_d, None, dropout, pair0 + a) if self.has_condition_encoder else None
@@ -666,8 +445,7 @@ class RegenModel:
         """gradients of sum(cond_logits * dlogits) over the given pairs: state-dict name -> tensor for condition_encoder.* and the
         two tables (the vector-Jacobian product of score()'s cond_logits).  backend="hip" runs csrc/regen_score_bwd.hip, chunked
         with `accumulate`; backend="torch" is autograd through the eager restatement in `dtype`"""
-        if backend not in ("hip", "torch"):
-            raise ValueError(f"backend must be 'hip' or 'torch', not {backend!r}")
+        _check_backend(backend)
         if not self.has_condition_encoder:
             raise ValueError("condition_grad needs condition_encoder.* and this state dict has none")
         _, _, tgt, tgt_len, _, T = self._pack_pairs(pairs, width)
@@ -679,20 +457,15 @@ class RegenModel:
         names = ["item_embedding.weight", "position_embedding.weight"] + [k for k in score_param_names() if k.startswith("condition_encoder.")]
         if backend == "hip":
             flat = None
-            for a in range(0, max(n, 1), COND_BWD_PAIRS_PER_CALL):
-                b = min(n, a + COND_BWD_PAIRS_PER_CALL)
+            # KEPT DIFFERENCE: this loop runs once for n = 0 (an empty call: the all-zero flat buffer the views below need); the
+            # other chunk loops do not run at all
+            for a, b in list(_chunks(n, COND_BWD_PAIRS_PER_CALL)) or [(0, 0)]:
                 flat = self.condition_bwd_device(tgt[a:b].to(dev).contiguous(), tgt_len[a:b].to(dev).contiguous(),
                                                  dlogits[a:b].to(dev, torch.float32).contiguous(), flat, accumulate=flat is not None,
                                                  dropout=dropout, pair0=pair0 + a)
             g = self.grads_from_flat(flat)
             return {k: g[k] for k in names}
-        leaves = {k: v.to(device=dev, dtype=dtype).clone().requires_grad_(k in names) for k, v in self.p.items()}
-        for a in range(0, n, ROWS_PER_TORCH):
-            b = min(n, a + ROWS_PER_TORCH)
-            _, c = self._score_torch(tgt[a:b, :1].to(dev), tgt[a:b].to(dev), tgt_len[a:b].to(dev), None, True, True, dtype, leaves,
-                                     _TorchDrop.of(dropout, pair0 + a, b - a, dtype, dev))
-            (c * dlogits[a:b].to(dev, dtype)).sum().backward()
-        return {k: (leaves[k].grad if leaves[k].grad is not None else torch.zeros_like(leaves[k])) for k in names}
+        return _torch().condition_grad(self, tgt, tgt_len, dlogits, names, dtype, dropout, pair0)
 
     def loss_and_grad(self, pairs, conditions, causal_source: bool = True, width=None, backend: str = "hip", dtype=torch.float32,
                       noise=None, tau: float = 1.0, entropy_weight: float = 0.0, dropout=None, pair0: int = 0):
@@ -708,8 +481,7 @@ class RegenModel:
         backend="hip": csrc/regen_score_bwd.hip, chunked at SCORE_BWD_PAIRS_PER_CALL pairs with `accumulate`; in "encoder" mode the
         few [n, K] operations between dw and the condition encoder's backward run in torch autograd on the device.
         backend="torch": autograd through the eager restatement, fp32 or fp64 (`dtype`): the float64 side of every check."""
-        if backend not in ("hip", "torch"):
-            raise ValueError(f"backend must be 'hip' or 'torch', not {backend!r}")
+        _check_backend(backend)
         src, src_len, tgt, tgt_len, Ls, T = self._pack_pairs(pairs, width)
         n = len(pairs)
         for i in range(n):
@@ -731,42 +503,8 @@ class RegenModel:
         if backend == "hip":
             return self._loss_and_grad_hip(src, src_len, tgt, tgt_len, T, conditions, causal_source, noise, tau, entropy_weight, dropout,
                                            int(pair0))
-        dev = self.device
-        n_tok = max(int((tgt[:, 1:] != 0).sum()), 1)
-        leaves = {k: v.to(device=dev, dtype=dtype).clone().requires_grad_(True) for k, v in self.p.items()}
-        loss = torch.zeros((), dtype=torch.float64)
-        entropy = torch.zeros((), dtype=torch.float64)
-        dws, conds = [], []
-        for a in range(0, n, ROWS_PER_TORCH):
-            b = min(n, a + ROWS_PER_TORCH)
-            s_d, t_d, tl_d = src[a:b].to(dev), tgt[a:b].to(dev), tgt_len[a:b].to(dev)
-            ent = None
-            td = _TorchDrop.of(dropout, int(pair0) + a, b - a, dtype, dev)
-            if encoder:
-                _, c = self._score_torch(s_d, t_d, tl_d, None, True, causal_source, dtype, leaves, td)
-                z = c if noise is None else c + torch.as_tensor(noise)[a:b].to(dev, dtype)
-                w0 = torch.softmax(z / tau, -1)
-                ent = -(w0 * torch.log(w0 + 1e-12)).sum(-1).sum() / n
-                w = w0[None]                                          # its .grad is the cross entropy's alone: what the kernels call dw
-            else:
-                c = None
-                w = conditions[:, a:b].to(dev, dtype).clone().requires_grad_(True)
-            w.retain_grad()
-            nll, c2 = self._score_torch(s_d, t_d, tl_d, w, self.has_condition_encoder and c is None, causal_source, dtype, leaves, td)
-            ce = nll.sum() / n_tok
-            (ce if ent is None else ce + entropy_weight * ent).backward()
-            loss += float(ce.detach())
-            if ent is not None:
-                entropy += float(ent.detach())
-            dws.append(w.grad.detach())
-            c = c2 if c is None else c
-            if c is not None:
-                conds.append(c.detach())
-        grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-        n_w = 1 if encoder else conditions.shape[0]
-        return GradResult(loss, entropy if encoder else None, grads,
-                          torch.cat(dws, 1) if dws else torch.zeros(n_w, 0, self.K, dtype=dtype, device=dev),
-                          torch.cat(conds) if conds else None)
+        return _torch().loss_and_grad(self, src, tgt, tgt_len, conditions, causal_source, dtype, noise, tau, entropy_weight, dropout,
+                                      int(pair0))
 
     @torch.no_grad()
     def score(self, pairs, conditions="all", causal_source: bool = True, width=None, backend: str = "hip", dtype=torch.float32,
@@ -777,8 +515,7 @@ class RegenModel:
         [n_w, n_pair, K] tensor used as is.  causal_source=False scores with the bidirectional source encoder of stage 3.
         width=(Ls, T) scores at those matrix widths (a slice of a file scores as inside the file).  `dtype` applies to
         backend="torch" only.  dropout (a RegenDropout) scores in train mode: pair i takes the masks of global pair pair0 + i."""
-        if backend not in ("hip", "torch"):
-            raise ValueError(f"backend must be 'hip' or 'torch', not {backend!r}")
+        _check_backend(backend)
         src, src_len, tgt, tgt_len, Ls, T = self._pack_pairs(pairs, width)
         n = len(pairs)
         pair0 = int(pair0)
@@ -792,72 +529,30 @@ class RegenModel:
             w = torch.as_tensor(conditions)
             if tuple(w.shape[1:]) != (n, self.K) or w.dim() != 3:
                 raise ValueError(f"condition weights of shape {tuple(w.shape)}, expected [n_w, {n}, {self.K}]")
-        hip = backend == "hip"
-        odt = torch.float32 if hip else dtype
         dev = self.device
-        nll, cond = [], []
-        for a in range(0, n, PAIRS_PER_CALL if hip else ROWS_PER_TORCH):
-            b = min(n, a + (PAIRS_PER_CALL if hip else ROWS_PER_TORCH))
-            s_d, t_d, tl_d = src[a:b].to(dev).contiguous(), tgt[a:b].to(dev).contiguous(), tgt_len[a:b].to(dev).contiguous()
-            wc = None if w is None else w[:, a:b]
-            if hip:
+        if backend == "torch":
+            nll, cond = _torch().score(self, src, tgt, tgt_len, w, causal_source, dtype, dropout, pair0)
+        else:
+            dtype = torch.float32
+            nll, cond = [], []
+            for a, b in _chunks(n, PAIRS_PER_CALL):
+                s_d, sl_d = src[a:b].to(dev).contiguous(), src_len[a:b].to(dev).contiguous()
+                t_d, tl_d = tgt[a:b].to(dev).contiguous(), tgt_len[a:b].to(dev).contiguous()
                 c = self.condition_device(t_d, tl_d, None, dropout, pair0 + a) if self.has_condition_encoder else None
-                if wc is None:
-                    wc = torch.softmax(c, -1)[None]
-                wc = wc.to(dev, torch.float32).contiguous()
-                x = self.score_device(s_d, src_len[a:b].to(dev).contiguous(), t_d, tl_d, wc, causal_source, None, dropout, pair0 + a)
-            else:
-                c = None
-                td = _TorchDrop.of(dropout, pair0 + a, b - a, dtype, dev)
-                if wc is None:
-                    _, c = self._score_torch(s_d, t_d, tl_d, None, True, causal_source, dtype, None, td)
-                    wc = torch.softmax(c, -1)[None]
-                x, c2 = self._score_torch(s_d, t_d, tl_d, wc, self.has_condition_encoder and c is None, causal_source, dtype, None, td)
-                c = c2 if c is None else c
-            nll.append(x.cpu())
-            if c is not None:
-                cond.append(c.cpu())
+                wc = torch.softmax(c, -1)[None] if w is None else w[:, a:b]
+                nll.append(self.score_device(s_d, sl_d, t_d, tl_d, wc.to(dev, torch.float32).contiguous(), causal_source, None, dropout,
+                                             pair0 + a).cpu())
+                if c is not None:
+                    cond.append(c.cpu())
         n_w = 1 if w is None else w.shape[0]
-        nll = torch.cat(nll, 1) if nll else torch.zeros(n_w, 0, T, dtype=odt)
+        nll = torch.cat(nll, 1) if nll else torch.zeros(n_w, 0, T, dtype=dtype)
         return ScoreResult(nll, (tgt[:, 1:] != 0).sum(1), torch.cat(cond) if cond else None, Ls, T)
-
-
-def _eval_mode(dropout):
-    """None and p = 0 are eval mode: the entry points without dropout, bit for bit"""
-    if dropout is not None and not isinstance(dropout, RegenDropout):
-        raise TypeError(f"dropout must be a RegenDropout or None, not {type(dropout).__name__}")
-    return dropout is None or dropout.p == 0.0
 
 
 def _drop_args(dropout, pair0):
     if int(pair0) < 0:
         raise ValueError("pair0 must not be negative")
     return C.c_float(dropout.p), C.c_uint64(dropout.seed), C.c_uint32(dropout.step), C.c_int64(int(pair0))
-
-
-class _TorchDrop:
-    """the keep factors of one torch batch (global pairs pair0 .. pair0 + n - 1) as tensors, from the host mirror of the kernels'
-    masks (regen_dropout.py); a site is "src_emb", "tgt_emb" or (stack, layer, kind)"""
-
-    def __init__(self, dropout, pair0, n, dtype, device):
-        self.d, self.pairs, self.dtype, self.device, self.cache = dropout, range(pair0, pair0 + n), dtype, device, {}
-
-    @staticmethod
-    def of(dropout, pair0, n, dtype, device):
-        return None if _eval_mode(dropout) else _TorchDrop(dropout, pair0, n, dtype, device)
-
-    def _get(self, fn, s, shape):
-        sid = {"src_emb": regen_dropout.SITE_SRC_EMB, "tgt_emb": regen_dropout.SITE_TGT_EMB}[s] if isinstance(s, str) else regen_dropout.site(*s)
-        key = (sid, shape)
-        if key not in self.cache:
-            self.cache[key] = torch.from_numpy(fn(self.d, sid, list(self.pairs), *shape)).to(device=self.device, dtype=self.dtype)
-        return self.cache[key]
-
-    def rows(self, s, x):
-        return self._get(regen_dropout.keep_rows, s, tuple(x.shape[1:]))
-
-    def probs(self, s, a):
-        return self._get(regen_dropout.keep_probs, s, tuple(a.shape[2:]))
 
 
 class GradResult:
@@ -890,19 +585,14 @@ def random_state_dict(n_item: int = NUM_ITEM["toy"], K: int = 5, seed: int = 0, 
     """a seeded random regenerator state dict in the reference's names (normal weights, LayerNorm weight 1 / bias 0): the
     measurement's worst case (no row stops early) and the synthetic cross-checks' model"""
     g = torch.Generator().manual_seed(seed)
+    names, shapes = (score_param_names(), score_param_shapes(n_item + 2, K)) if condition_encoder else (param_names(), param_shapes(n_item + 2, K))
     sd = {}
-    for name, shape in zip(param_names(), param_shapes(n_item + 2, K)):
-        if name.split(".")[-2].startswith("norm") or name.startswith("transformer.encoder.norm") or name.startswith("transformer.decoder.norm"):
+    for name, shape in zip(names, shapes):     # condition_encoder.* is drawn after everything else: the other tensors do not depend on the flag
+        if name.split(".")[-2].startswith("norm"):
             sd[name] = torch.ones(shape) if name.endswith("weight") else torch.zeros(shape)
         else:
             sd[name] = std * torch.randn(shape, generator=g)
     sd["item_embedding_decoder.weight"] = sd["item_embedding.weight"]
-    if condition_encoder:      # drawn after everything else: the tensors above do not depend on this flag
-        for name, shape in list(zip(score_param_names(), score_param_shapes(n_item + 2, K)))[len(param_names()):]:
-            if name.split(".")[-2].startswith("norm"):
-                sd[name] = torch.ones(shape) if name.endswith("weight") else torch.zeros(shape)
-            else:
-                sd[name] = std * torch.randn(shape, generator=g)
     return sd
 
 

@@ -2,7 +2,7 @@
 
 The kernels (csrc/regen_score_fwd.h, DropPhilox) regenerate every mask from (seed, step, site, element index) with the project's
 Philox4x32-10 convention (csrc/common.h: one call covers 8 consecutive elements, 16-bit decisions, keep iff r16 >= round(p * 65536)).
-This module is the exactly-equal host side: the torch restatement (RegenModel._score_torch) and the reference fixture
+This module is the exactly-equal host side: the torch restatement (regen_torch.score_forward) and the reference fixture
 (tools/make_regen_train_golden.py) multiply by what keep_* return, so a float64 run sees the masks the HIP run sees.
 
 Sites (DESIGN.md has the table): site(stack, layer, kind) with stack 0 source encoder, 1 condition encoder, 2 decoder;
@@ -66,6 +66,13 @@ class RegenDropout:
 
     def scale(self) -> np.float32:
         return np.float32(1.0) / (np.float32(1.0) - np.float32(self.p))
+
+
+def eval_mode(dropout) -> bool:
+    """None and p = 0 are eval mode: the entry points without dropout, bit for bit"""
+    if dropout is not None and not isinstance(dropout, RegenDropout):
+        raise TypeError(f"dropout must be a RegenDropout or None, not {type(dropout).__name__}")
+    return dropout is None or dropout.p == 0.0
 
 
 def philox4x32_10(c0, c1, c2, c3, seed: int):

@@ -148,7 +148,7 @@ class RegenTrainer:
         self.n_pad = (self.n_params + 3) // 4 * 4
         self.params = torch.zeros(self.n_pad, dtype=torch.float32, device=dev)
         self.params[:self.n_params] = flat
-        model._score_flat = self.params[:self.n_params]
+        model.adopt_score_flat(self.params[:self.n_params])
         self.grads = torch.zeros(self.n_pad + _lib.GRAD_TAIL, dtype=torch.float32, device=dev)
         self.grads[self.n_pad] = 1.0                                 # the tail {normaliser 1 (the gradient is already the mean's), 0, poison 0, 0}
         self.adam_m = torch.zeros(self.n_pad, dtype=torch.float32, device=dev)

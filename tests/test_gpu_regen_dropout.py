@@ -142,6 +142,7 @@ def test_train_mode_forward_on_the_fixture_pairs():
 def relu_inputs(m, src, tgt, tgt_len, w, dt, td, causal):
     """the inputs of both ReLUs (condition_linear[0]: [n, Ls, 64 K]; condition_layer[0]: [n, 64]) of the eager restatement at dtype dt"""
     import torch.nn.functional as F
+    from dr4sr_amd import regen_torch
     p = m._params_as(dt, src.device)
     names = {id(p["condition_linear.0.weight"]): "mem", id(p["condition_encoder.condition_layer.0.weight"]): "cond"}
     cap, orig = {}, F.linear
@@ -154,7 +155,7 @@ def relu_inputs(m, src, tgt, tgt_len, w, dt, td, causal):
 
     F.linear = lin
     try:
-        m._score_torch(src, tgt, tgt_len, w.to(dt), True, causal, dt, None, td)
+        regen_torch.score_forward(m, src, tgt, tgt_len, w.to(dt), True, causal, dt, None, td)
     finally:
         F.linear = orig
     return cap["mem"], cap["cond"]
@@ -167,12 +168,12 @@ def select_pairs(m, cand, n_keep, d, seed, causal):
     len(cand) = 2 n_keep, so at most half may be dropped, the share the existing test allows.  The masks follow the pair index (a
     source's position 0 sees only SOS and its own masks, so an index can be near a ReLU step whatever pair sits there): the kept pairs are
     used at their candidate indices."""
-    from dr4sr_amd.regen import _TorchDrop
+    from dr4sr_amd.regen_torch import TorchDrop
     n, dev = len(cand), m.device
     w = weights(1, n, m.K, seed).to(dev)
     src, src_len, tgt, tgt_len, Ls, T = m._pack_pairs(cand, None)
     src, src_len, tgt, tgt_len = (t.to(dev) for t in (src, src_len, tgt, tgt_len))
-    pre = {dt: relu_inputs(m, src, tgt, tgt_len, w, dt, _TorchDrop.of(d, 0, n, dt, dev), causal) for dt in (torch.float32, torch.float64)}
+    pre = {dt: relu_inputs(m, src, tgt, tgt_len, w, dt, TorchDrop.of(d, 0, n, dt, dev), causal) for dt in (torch.float32, torch.float64)}
     live = (torch.arange(Ls, device=dev)[None, :] < src_len[:, None])[:, :, None].expand_as(pre[torch.float64][0])
     noise_m = float((pre[torch.float32][0].double() - pre[torch.float64][0])[live].abs().max())
     noise_c = float((pre[torch.float32][1].double() - pre[torch.float64][1]).abs().max())

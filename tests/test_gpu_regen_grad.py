@@ -223,10 +223,11 @@ def score_inputs(m, pairs, n_w, seed):
 
 def autograd_of_weighted_nll(m, dev, w, dnll):
     """{dtype: {name: gradient}} of sum(nll * dnll) through the eager restatement in fp32 and float64"""
+    from dr4sr_amd import regen_torch
     unit = {}
     for dt in (torch.float32, torch.float64):
         leaves = {k: v.to(dt).clone().requires_grad_(True) for k, v in m.p.items()}
-        nll, _ = m._score_torch(dev[0], dev[2], dev[3], w.to(dt), False, True, dt, leaves)
+        nll, _ = regen_torch.score_forward(m, dev[0], dev[2], dev[3], w.to(dt), False, True, dt, leaves)
         (nll * dnll.to(dt)).sum().backward()
         unit[dt] = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
     return unit
@@ -303,6 +304,7 @@ def test_a_random_upstream_gradient_matches_float64_per_tensor():
 def relu_inputs(m, dev, w, dt):
     """the inputs of condition_linear's ReLU [n, Ls, 320] in the eager restatement at dtype dt"""
     import torch.nn.functional as F
+    from dr4sr_amd import regen_torch
     src, _, tgt, tgt_len = dev
     p = m._params_as(dt, src.device)
     cap, orig = {}, F.linear
@@ -315,7 +317,7 @@ def relu_inputs(m, dev, w, dt):
 
     F.linear = lin
     try:
-        m._score_torch(src, tgt, tgt_len, w.to(dt), False, True, dt)
+        regen_torch.score_forward(m, src, tgt, tgt_len, w.to(dt), False, True, dt)
     finally:
         F.linear = orig
     return cap["y"]

@@ -52,7 +52,7 @@ def mirror_noise(step, n, seed=SEED):
 
 
 class HookDrop:
-    """RegenModel's _TorchDrop with the masks from the device hook: the whole (seed, step, site) stream from element 0 up to the last
+    """regen_torch's TorchDrop with the masks from the device hook: the whole (seed, step, site) stream from element 0 up to the last
     pair, cut to the pairs and the shape asked for"""
 
     def __init__(self, d, pair0, n, dtype, device):
@@ -81,18 +81,19 @@ class HookDrop:
 @pytest.fixture
 def hook_masks(monkeypatch):
     """loss_and_grad(backend="torch") with HookDrop masks"""
-    from dr4sr_amd import regen
+    from dr4sr_amd import regen_dropout, regen_torch
 
     def of(dropout, pair0, n, dtype, device):
-        return None if regen._eval_mode(dropout) else HookDrop(dropout, pair0, n, dtype, device)
+        return None if regen_dropout.eval_mode(dropout) else HookDrop(dropout, pair0, n, dtype, device)
 
-    monkeypatch.setattr(regen._TorchDrop, "of", staticmethod(of))
+    monkeypatch.setattr(regen_torch.TorchDrop, "of", staticmethod(of))
 
 
 def test_hook_masks_are_the_mirror_masks():
-    from dr4sr_amd.regen import RegenDropout, _TorchDrop
+    from dr4sr_amd.regen import RegenDropout
+    from dr4sr_amd.regen_torch import TorchDrop
     d = RegenDropout(0.5, SEED, 3)
-    a, b = HookDrop(d, 2, 9, torch.float64, "cuda"), _TorchDrop(d, 2, 9, torch.float64, "cuda")
+    a, b = HookDrop(d, 2, 9, torch.float64, "cuda"), TorchDrop(d, 2, 9, torch.float64, "cuda")
     for s, x in (("tgt_emb", torch.empty(9, 19, 64)), ((2, 1, 4), torch.empty(9, 19, 256)), ((0, 0, 3), torch.empty(9, 50, 64))):
         assert torch.equal(a.rows(s, x), b.rows(s, x)), s
     for s, x in (((2, 0, 2), torch.empty(9, 2, 19, 50)), ((1, 1, 0), torch.empty(9, 2, 19, 19))):
@@ -228,15 +229,16 @@ def torch_side(m, batch, good, n_tok, noise, tau, d, dt):
     """what loss_and_grad(backend="torch") differentiates, written out so that the scalar can leave pairs out: the gradient of
     sum over the GOOD pairs of (their token NLLs / n_tok + their entropy term / n_batch), n_tok and n_batch of the whole batch; with every
     pair good this is loss_and_grad's CE + 1 x entropy.  Returns (grads by name, CE of the whole batch, mean entropy of the whole batch)"""
+    from dr4sr_amd import regen_torch
     dev, nb = m.device, len(batch)
     src, src_len, tgt, tgt_len, Ls, T = m._pack_pairs(batch, WIDTH)
     src, tgt, tgt_len = src.to(dev), tgt.to(dev), tgt_len.to(dev)
     leaves = {k: v.to(dt).clone().requires_grad_(True) for k, v in m.p.items()}
     td = HookDrop(d, 0, nb, dt, dev)
-    _, c = m._score_torch(src, tgt, tgt_len, None, True, True, dt, leaves, td)
+    _, c = regen_torch.score_forward(m, src, tgt, tgt_len, None, True, True, dt, leaves, td)
     w0 = torch.softmax((c + noise.to(dev, dt)) / tau, -1)
     ent = -(w0 * torch.log(w0 + 1e-12)).sum(-1)
-    nll, _ = m._score_torch(src, tgt, tgt_len, w0[None], False, True, dt, leaves, td)
+    nll, _ = regen_torch.score_forward(m, src, tgt, tgt_len, w0[None], False, True, dt, leaves, td)
     g = good.to(dev, dt)
     ((nll[0].sum(-1) * g).sum() / n_tok + (ent * g).sum() / nb).backward()
     grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}

@@ -58,6 +58,7 @@ def test_loss_is_the_scored_loss_and_the_result_is_complete():
 
 @pytest.mark.parametrize("causal", [True, False])
 def test_central_finite_differences_in_float64(causal):
+    from dr4sr_amd import regen_torch
     m = small_model()
     pairs = small_pairs(6, m.n_item, 1)
     g = torch.Generator().manual_seed(3)
@@ -77,9 +78,9 @@ def test_central_finite_differences_in_float64(causal):
             p64 = m._params_as(torch.float64, torch.device("cpu"))
             p64[name][idx] += sgn * h
             src, src_len, tgt, tgt_len, _, _ = m._pack_pairs(pairs, None)
-            _, c = m._score_torch(src, tgt, tgt_len, None, True, causal, torch.float64, p64)
+            _, c = regen_torch.score_forward(m, src, tgt, tgt_len, None, True, causal, torch.float64, p64)
             w = torch.softmax((c + noise) / 0.7, -1)[None]
-            nll, _ = m._score_torch(src, tgt, tgt_len, w, False, causal, torch.float64, p64)
+            nll, _ = regen_torch.score_forward(m, src, tgt, tgt_len, w, False, causal, torch.float64, p64)
             vals.append(float(nll.sum() / (tgt[:, 1:] != 0).sum() - (w[0] * torch.log(w[0] + 1e-12)).sum(-1).mean()))
         m._cast.clear()
         assert torch.equal(m.p[name], base)
@@ -157,6 +158,23 @@ def test_load_params_round_trip_keeps_the_buffers():
         m.load_params({"no.such.tensor": torch.zeros(1)})
     with pytest.raises(ValueError):
         m.load_params({"condition_linear.2.bias": torch.zeros(3)})
+
+
+def test_adopt_score_flat_takes_a_checked_buffer_and_load_params_writes_through_it():
+    m = small_model()
+    n = m.score_flat().numel()
+    master = torch.zeros(n + 3)                                        # a trainer's padded master: the model's buffer is a view of it
+    master[:n] = m.score_flat()
+    m.adopt_score_flat(master[:n])
+    plan = m.score_plan()
+    assert (m.score_flat().data_ptr(), plan.params, plan.n_params) == (master.data_ptr(), master.data_ptr(), n)
+    m.load_params({"condition_linear.2.bias": torch.full_like(m.p["condition_linear.2.bias"], 0.25)})
+    assert torch.equal(m.grads_from_flat(master[:n])["condition_linear.2.bias"], m.p["condition_linear.2.bias"])
+    assert float(master[n:].abs().max()) == 0.0
+    for bad in (torch.zeros(n + 1), torch.zeros(n, dtype=torch.float64), torch.zeros(2 * n)[::2], torch.zeros(1, n), torch.zeros(n, device="meta")):
+        with pytest.raises(ValueError, match="score buffer"):
+            m.adopt_score_flat(bad)
+    assert m.score_flat().data_ptr() == master.data_ptr()
 
 
 def test_argument_errors_of_the_backward_entry_points():

@@ -39,7 +39,7 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--loop-sample", type=int, default=200)
     a = ap.parse_args()
-    from dr4sr_amd import regen
+    from dr4sr_amd import regen, regen_torch
     dev = torch.device("cuda", 0)
     if a.fixture:
         z = np.load(a.fixture)
@@ -91,7 +91,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i, c in zip(picks, conds):
-            m._decode_torch(src[i:i + 1, :int(lens[i])], lens[i:i + 1], int(c), 1)
+            regen_torch.decode(m, src[i:i + 1, :int(lens[i])], lens[i:i + 1], int(c), 1)
         torch.cuda.synchronize()
         per = (time.perf_counter() - t0) / a.loop_sample
         res["loop_per_decode_s"] = round(per, 5)

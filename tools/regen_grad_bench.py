@@ -38,7 +38,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
-    from dr4sr_amd import regen
+    from dr4sr_amd import regen, regen_torch
     from regen_score_bench import median_ms, toys_pairs
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -107,11 +107,11 @@ def main():
                 for lo in range(0, n, regen.ROWS_PER_TORCH):
                     s, t, tl = (x[lo:lo + regen.ROWS_PER_TORCH].to(dev) for x in (src, tgt, tgt_len))
                     hi = lo + s.shape[0]
-                    c = m._score_torch(s, t, tl, None, True, True, torch.float32, leaves, tdrop)[1] if mode == "encoder" else None
+                    c = regen_torch.score_forward(m, s, t, tl, None, True, True, torch.float32, leaves, tdrop)[1] if mode == "encoder" else None
                     w, w0, ent = weights_of(c, lo, hi)
                     if mode == "encoder":
                         w = w0[None]
-                    nll, _ = m._score_torch(s, t, tl, w, False, True, torch.float32, leaves, tdrop)
+                    nll, _ = regen_torch.score_forward(m, s, t, tl, w, False, True, torch.float32, leaves, tdrop)
                     (nll.sum() / n_tok + (ent if ent is not None else 0.0)).backward()
 
             r = {"metric": "regen_loss_and_grad", "mode": mode, "pairs": n, "n_w": n_w, "live_tokens": n_tok * n_w, "K": m.K, "width": [Ls, T],

@@ -66,7 +66,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
-    from dr4sr_amd import regen
+    from dr4sr_amd import regen, regen_torch
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     m = regen.RegenModel.from_state_dict(regen.random_state_dict(seed=3, std=0.3, condition_encoder=True), dev)
@@ -112,7 +112,7 @@ def main():
         def run_torch():
             with torch.no_grad():
                 for s, sl, t, tl, w in torch_chunks:
-                    m._score_torch(s, t, tl, w, True, True, torch.float32)
+                    regen_torch.score_forward(m, s, t, tl, w, True, True, torch.float32)
 
         med_t, lo_t, hi_t = median_ms(torch, run_torch, 1, a.torch_repeats)
         r.update(torch_ms=round(med_t, 3), torch_ms_min=round(lo_t, 3), torch_ms_max=round(hi_t, 3), torch_repeats=a.torch_repeats,

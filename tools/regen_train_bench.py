@@ -38,7 +38,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "regen_train_bench.json"))
     a = ap.parse_args()
     import torch
-    from dr4sr_amd import regen
+    from dr4sr_amd import regen, regen_torch
     from dr4sr_amd.regen_train import RegenTrainer, lr_at, tau_at
     from regen_score_bench import toys_pairs
     dev = torch.device("cuda", 0)
@@ -108,10 +108,10 @@ def main():
             idx = idx.to(dev)
             src, tgt, tl = src_d[idx], tgt_d[idx], tl_d[idx]
             t_opt.zero_grad(set_to_none=True)
-            c = tm._score_torch(src, tgt, tl, None, True, True, torch.float32, leaves, tdrop)[1]
+            c = regen_torch.score_forward(tm, src, tgt, tl, None, True, True, torch.float32, leaves, tdrop)[1]
             w0 = torch.softmax((c + gumbel(a.batch)) / tau_at(s), -1)
             ent = -(w0 * torch.log(w0 + 1e-12)).sum(-1).mean()
-            nll, _ = tm._score_torch(src, tgt, tl, w0[None], False, True, torch.float32, leaves, tdrop)
+            nll, _ = regen_torch.score_forward(tm, src, tgt, tl, w0[None], False, True, torch.float32, leaves, tdrop)
             (nll.sum() / n_tok + ent).backward()
             for g in t_opt.param_groups:
                 g["lr"] = lr_at(s, 1e-3, epochs)
