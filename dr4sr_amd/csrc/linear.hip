@@ -375,7 +375,9 @@ __device__ __forceinline__ float4 keep_factors4(const RngKey& k, uint32_t bits) 
 //   yreg (optional): the LayerNorm output rows of THIS thread ([pass][D/64] float4, zero beyond T) — with OUT == NULL nothing of
 //   them goes to global memory (the fused last layer hands them to the scorer in registers)
 //   CARRY (one pass, one float4 per thread): v, (mean, rstd) and the keep bits of this thread's row are left in *cy as well
-template <int BM, int D, bool RES_IN_LDS, bool COPY_LDS, bool CARRY = false>
+//   KPRE (with CARRY): the keep bits ARRIVE in cy->keep (row_keep_word below) — no Philox call here —, and a residual row in global memory
+//   arrives in cy->v (requested at kernel entry)
+template <int BM, int D, bool RES_IN_LDS, bool COPY_LDS, bool CARRY = false, bool KPRE = false>
 __device__ __forceinline__ void ln_rowpass(const float* __restrict__ Cs, int ldc, const float* res, int ldres,
                                            const float* __restrict__ lnw, const float* __restrict__ lnb, float eps,
                                            float* __restrict__ U, float* __restrict__ OUT, float* __restrict__ ST,
@@ -383,6 +385,7 @@ __device__ __forceinline__ void ln_rowpass(const float* __restrict__ Cs, int ldc
                                            uint32_t site, float4 (*yreg)[D / 64] = nullptr, LnCarry* cy = nullptr) {
     constexpr int NV = D / 64, PASSES = BM / 16;
     static_assert(!CARRY || (NV == 1 && PASSES == 1), "the carried row state is one float4 per thread");
+    static_assert(!KPRE || CARRY, "the keep bits arrive in the carried row state");
     const int l16 = threadIdx.x & 15, rsub = threadIdx.x >> 4;
     float4 gam[NV], bet[NV], v[PASSES][NV];
     float mean[PASSES], rstd[PASSES];
@@ -398,10 +401,13 @@ __device__ __forceinline__ void ln_rowpass(const float* __restrict__ Cs, int ldc
             float4 o = ld4(Cs + row * ldc + c);
             float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
             if (RES_IN_LDS) r = ld4(res + row * ldres + c);
+            else if constexpr (KPRE) r = cy->v;
             else if (ok) r = ld4(res + (size_t)t * ldres + c);
             if (dodrop) {
-                const float4 m = drop4(rk, site, (uint64_t)t * D + c); o.x *= m.x; o.y *= m.y; o.z *= m.z; o.w *= m.w;
-                if constexpr (CARRY) cy->keep = keep_bits4(m);
+                float4 m;
+                if constexpr (KPRE) m = keep_factors4(rk, cy->keep); else m = drop4(rk, site, (uint64_t)t * D + c);
+                o.x *= m.x; o.y *= m.y; o.z *= m.z; o.w *= m.w;
+                if constexpr (CARRY && !KPRE) cy->keep = keep_bits4(m);
             }
             v[ps][j] = make_float4(r.x + o.x, r.y + o.y, r.z + o.z, r.w + o.w);
             if (ok) st4(U + (size_t)t * D + c, v[ps][j]);
@@ -435,7 +441,27 @@ __device__ __forceinline__ void row_keep_store(const PostArgs& A, const RowCarry
     const int t = t0 + (threadIdx.x >> 4);
     if (t < T) A.row_keep[16 * (size_t)t + (threadIdx.x & 15)] = (unsigned short)(cy.ln1.keep | (cy.ln2.keep << 4) | (cy.akeep << 8));
 }
-template <int BM, int D, int F, bool FFN_ONLY, bool KEEPQ = false, int CARRY = 0>
+// The same 16 bits from TWO Philox calls per thread, ahead of the passes (KU forms of post_fwd_body).  A call covers eight consecutive
+// elements, a thread owns four: lanes 2k and 2k + 1 of a row group need the same call of every site, and drop4 makes each of them run it and
+// throw half away (4 calls per thread for 16 decisions).  Here the even lane runs the call of sP and the call of sA's first float4
+// (j = 0), the odd lane the same call index of sF and the call of sA's second float4 (j = 1); each keeps the nibble of its own four columns
+// (even: low, odd: high) and hands the other nibble of both bytes to its partner.  Bit k of a nibble is drop4's decision for element c + k
+// (drop_bits8).  Every lane of the wave executes the exchange: call it outside any t < T guard.  No activation dropout: those bits are ones.
+__device__ __forceinline__ uint32_t row_keep_word(const RngKey& rk, const uint32_t sP, const uint32_t sF, const uint32_t sA, const bool actdrop, const int t) {
+    constexpr int D = 64, F = 128;
+    const int l16 = threadIdx.x & 15, pr = l16 >> 1;
+    const bool odd = l16 & 1;
+    const uint32_t b0 = drop_bits8(rk, odd ? sF : sP, (uint64_t)t * D + 8 * pr);
+    const uint32_t b1 = actdrop ? drop_bits8(rk, sA, (uint64_t)t * F + (odd ? 64 : 0) + 8 * pr) : 0xffu;
+    const uint32_t own0 = odd ? b0 >> 4 : b0 & 15u, own1 = odd ? b1 >> 4 : b1 & 15u;
+    const uint32_t give = odd ? (b0 & 15u) | ((b1 & 15u) << 4) : (b0 >> 4) | (b1 & 0xf0u);
+    const uint32_t got = (uint32_t)__shfl_xor((int)give, 1, 64), got0 = got & 15u, got1 = got >> 4;
+    return odd ? got0 | (own0 << 4) | (got1 << 8) | (own1 << 12) : own0 | (got0 << 4) | (own1 << 8) | (got1 << 12);
+}
+// KU (host: row_keep_saved; 16-row tiles, d = 64, F = 128, training with dropout, CARRY 1 | 2): the three row passes take their keep decisions
+// from ONE word computed ahead of them (row_keep_word: two Philox calls per thread instead of four, none inside the GELU and LayerNorm2 passes,
+// which touch no global memory and hide nothing), and LayerNorm1's residual row is requested at kernel entry.
+template <int BM, int D, int F, bool FFN_ONLY, bool KEEPQ = false, int CARRY = 0, bool KU = false>
 __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, const int T, float4 (*zreg)[D / 64] = nullptr,
                                               tattn::Keep* keep_out = nullptr, RowCarry<F>* cy = nullptr) {
     constexpr int LD = D + 4, LF = F + 4, NVF = F / 64, PASSES = BM / 16;
@@ -457,6 +483,18 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
     WFragT<PF ? F : 16, PF ? D : 64> f_w2;
     WFragT<PF ? D : 16, PF ? 3 * D : 64> f_nx;
     STAMP(0);
+    static_assert(!KU || (BM == 16 && D == 64 && F == 128 && !FFN_ONLY && CARRY != 0), "one row, one float4, 16 keep bits per thread");
+    auto keep_upfront = [&]() {
+        if constexpr (KU) {
+            const uint32_t w = row_keep_word(rk, sP, sF, sA, actdrop, t0 + rsub);
+            cy->ln1.keep = w & 15u; cy->ln2.keep = (w >> 4) & 15u; cy->akeep = w >> 8;
+        }
+    };
+    if constexpr (KU) {                        // LayerNorm1's residual row: its address needs t0 only (as k_post_bwd<.., KB> requests its row state)
+        const int t = t0 + rsub;
+        cy->ln1.v = t < T ? ld4(A.x + (size_t)t * D + 4 * l16) : make_float4(0.f, 0.f, 0.f, 0.f);
+        __builtin_amdgcn_sched_barrier(0);
+    }
     if (FFN_ONLY) {                            // FMLP Intermediate block: the input tile IS y
         load_tile_bm<BM, D>(R1, LD, A.x, D, t0, T);
     } else {
@@ -473,12 +511,16 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
 #else
         constexpr bool SPREAD = AT && PF;
 #endif
+        // the keep word beside own_keep, while the window is in flight (measured against right in front of the LayerNorm1 pass, the form
+        // the plans without the spread requests take: NOTEBOOK "One Philox call per eight dropout decisions")
+        constexpr bool KU_EARLY = KU && SPREAD;
         if constexpr (SPREAD) {
             if (at_on) {
                 tattn::fwd_issue<D, KEEPQ>(A, t0, T, att_pre);
                 __builtin_amdgcn_sched_barrier(0);
                 { if constexpr (D == 128) wfrag_load_img(f_out, reinterpret_cast<const float*>(A.sp) + WSplitGeo<D, F>::OUT); else wfrag_load(f_out, A.out_w, D); }
                 __builtin_amdgcn_sched_barrier(0);
+                if constexpr (KU_EARLY) { keep_upfront(); __builtin_amdgcn_sched_barrier(0); }      // beside own_keep: while the window is in flight
                 tattn::fwd_stage<D, KEEPQ>(A, t0, T, smem + att_lds_off(D, F), att_pre);
                 __builtin_amdgcn_sched_barrier(0);
                 { if constexpr (D == 128) wfrag_load_img(f_w1, reinterpret_cast<const float*>(A.sp) + WSplitGeo<D, F>::W1); else wfrag_load(f_w1, A.w1, D); }
@@ -493,6 +535,7 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
                 { if constexpr (D == 128) wfrag_load_img(f_w1, reinterpret_cast<const float*>(A.sp) + WSplitGeo<D, F>::W1); else wfrag_load(f_w1, A.w1, D); }
                 { if constexpr (D == 128) wfrag_load_img(f_w2, reinterpret_cast<const float*>(A.sp) + WSplitGeo<D, F>::W2); else wfrag_load(f_w2, A.w2, F); }
                 if (A.nx_qkv) { if constexpr (D == 128) wfrag_load_img(f_nx, reinterpret_cast<const float*>(A.sp) + WSplitGeo<D, F>::E); else wfrag_load(f_nx, A.nx_in_w, D); }
+                if constexpr (KU_EARLY) keep_upfront();
             }
         } else {
             constexpr bool EARLY = D == 128;               // (window before the fragments: no register spill at d = 128)
@@ -521,9 +564,10 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
             tile_to_lds<BM, D>(acc, R2, LD, A.out_b);
         }
         lds_barrier(); STAMP(2);
+        if constexpr (KU && !KU_EARLY) keep_upfront();
         // ---- dropout1 + residual + LayerNorm1
-        ln_rowpass<BM, D, false, true, CARRY != 0>(R2, LD, A.x, D, A.ln1_w, A.ln1_b, A.eps, A.u1, A.y, A.st1, R1, LD, t0, T, dodrop, rk, sP, nullptr,
-                                              CARRY ? &cy->ln1 : nullptr);
+        ln_rowpass<BM, D, false, true, CARRY != 0, KU>(R2, LD, A.x, D, A.ln1_w, A.ln1_b, A.eps, A.u1, A.y, A.st1, R1, LD, t0, T, dodrop, rk, sP, nullptr,
+                                                  CARRY ? &cy->ln1 : nullptr);
     }
     lds_barrier(); STAMP(3);
     // ---- linear1 + GELU + dropout
@@ -550,10 +594,12 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
                 const int c = 4 * l16 + 64 * j;
                 const float4 a4 = av[ps][j];
                 float4 h = make_float4(gelu_erf(a4.x), gelu_erf(a4.y), gelu_erf(a4.z), gelu_erf(a4.w));
-                if constexpr (CARRY != 0) { cy->a[j] = a4; if (j == 0) cy->akeep = 0; }
+                if constexpr (CARRY != 0) { cy->a[j] = a4; if (j == 0 && !KU) cy->akeep = 0; }
                 if (actdrop) {
-                    const float4 m = drop4(rk, sA, (uint64_t)t * F + c); h.x *= m.x; h.y *= m.y; h.z *= m.z; h.w *= m.w;
-                    if constexpr (CARRY != 0) cy->akeep |= keep_bits4(m) << (4 * j);
+                    float4 m;
+                    if constexpr (KU) m = keep_factors4(rk, cy->akeep >> (4 * j)); else m = drop4(rk, sA, (uint64_t)t * F + c);
+                    h.x *= m.x; h.y *= m.y; h.z *= m.z; h.w *= m.w;
+                    if constexpr (CARRY != 0 && !KU) cy->akeep |= keep_bits4(m) << (4 * j);
                 }
                 if (ok) { st4(A.a + (size_t)t * F + c, a4); st4(A.h + (size_t)t * F + c, h); }
                 st4(R2 + row * LF + c, h);
@@ -571,7 +617,7 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
     }
     lds_barrier(); STAMP(6);
     if (!FFN_ONLY && A.nx_qkv) {               // layer-boundary fusion: keep z in LDS and emit the next layer's in_proj
-        ln_rowpass<BM, D, true, true, CARRY != 0>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, R1, LD, t0, T, dodrop, rk, sF, nullptr,
+        ln_rowpass<BM, D, true, true, CARRY != 0, KU>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, R1, LD, t0, T, dodrop, rk, sF, nullptr,
                                                   CARRY ? &cy->ln2 : nullptr);
         if constexpr (CARRY == 2) row_keep_store<F>(A, *cy, t0, T);
         lds_barrier();
@@ -582,7 +628,7 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
         tile_to_global<BM, 3 * D>(acc, A.nx_qkv, 3 * D, A.nx_in_b, t0, T);
         if (A.nx_dqkv_zero) zero_kv_rows<BM, D>(A.nx_dqkv_zero, t0, T);
     } else {
-        ln_rowpass<BM, D, true, false, CARRY != 0>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, nullptr, 0, t0, T, dodrop, rk, sF, zreg,
+        ln_rowpass<BM, D, true, false, CARRY != 0, KU>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, nullptr, 0, t0, T, dodrop, rk, sF, zreg,
                                                    CARRY ? &cy->ln2 : nullptr);
         if constexpr (CARRY == 2) row_keep_store<F>(A, *cy, t0, T);
     }
@@ -590,7 +636,8 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
 }
 
 // KB (host: row_keep_saved — training with dropout, 16-row tiles, d = 64, F = 128, fused step): the keep decisions of the three row passes are
-// stored for k_post_bwd<.., KB>; the two launches of a plan are paired by that ONE predicate
+// stored for k_post_bwd<.., KB>; the two launches of a plan are paired by that ONE predicate.  The same predicate selects the KU form of the
+// forward body (keep word ahead of the passes), here and in k_post_mid<.., KU>
 template <int BM, int D, int F, bool FFN_ONLY, bool KB = false>
 __global__ __launch_bounds__(256) void k_post_fwd(const PostArgs A) {
     const int T = A.state[DR4SR_STATE_T], t0 = xcd_tile(T, BM, A.xcd) * BM;
@@ -598,7 +645,7 @@ __global__ __launch_bounds__(256) void k_post_fwd(const PostArgs A) {
     if constexpr (KB) {
         RowCarry<F> cy;
         cy.ln1.keep = cy.ln2.keep = cy.akeep = 0;
-        post_fwd_body<BM, D, F, FFN_ONLY, false, 2>(A, t0, T, nullptr, nullptr, &cy);
+        post_fwd_body<BM, D, F, FFN_ONLY, false, 2, true>(A, t0, T, nullptr, nullptr, &cy);
     } else post_fwd_body<BM, D, F, FFN_ONLY>(A, t0, T);
 }
 
@@ -1375,7 +1422,7 @@ __device__ __forceinline__ void score_tile_regs(const PostArgs& A, const ScoreTi
     }
 }
 
-template <int BM, int D, int F, bool META, bool DET = false>
+template <int BM, int D, int F, bool META, bool DET = false, bool KU = false>
 __device__ __forceinline__ void post_mid_body(const PostArgs& A, const ScoreTileArgs& S) {
     const int T = A.state[DR4SR_STATE_T], bx = xcd_tile(T, BM, A.xcd), t0 = bx * BM;
     if (t0 >= T) return;
@@ -1389,7 +1436,7 @@ __device__ __forceinline__ void post_mid_body(const PostArgs& A, const ScoreTile
         tattn::Keep keep{0xffffffffu, 0xffffffffu};
         constexpr int CARRY = BM == 16 ? 1 : 0;              // latency regime: the row passes' state crosses the two halves in registers
         RowCarry<F> cy;
-        post_fwd_body<BM, D, F, false, true, CARRY>(Af, t0, T, zreg, &keep, &cy);
+        post_fwd_body<BM, D, F, false, true, CARRY, KU>(Af, t0, T, zreg, &keep, &cy);
         if constexpr (BM != 16) score_prefetch<BM>(A, S, t0, T, P);             // occupancy regime: its registers would cost a workgroup per CU
         if constexpr (META) lds_barrier();                   // every wave is past the forward half's last LDS reads: the tiles are free
         score_tile_regs<BM, META>(A, S, t0, T, bx, P, zreg, dzreg, smem + post_lds_floats(D, F, BM), smem);
@@ -1405,8 +1452,9 @@ __device__ __forceinline__ void post_mid_body(const PostArgs& A, const ScoreTile
         post_bwd_body<BM, D, F, false, DET>(A, t0, T, bx, nullptr, &keep);
     }
 }
-template <int BM, int D, int F, bool META, bool DET = false>
-__global__ __launch_bounds__(256) void k_post_mid(const PostArgs A, const ScoreTileArgs S) { post_mid_body<BM, D, F, META, DET>(A, S); }
+// KU (host: row_keep_saved, the predicate of k_post_fwd<.., KB>): keep word ahead of the row passes
+template <int BM, int D, int F, bool META, bool DET = false, bool KU = false>
+__global__ __launch_bounds__(256) void k_post_mid(const PostArgs A, const ScoreTileArgs S) { post_mid_body<BM, D, F, META, DET, KU>(A, S); }
 // The 32-row (at-scale) form with its registers capped at 128: the fused kernel carries the query / dz rows and the scorer's prefetch
 // across its two halves (160 VGPRs: 3 waves per SIMD, where k_post_fwd / k_post_bwd run 4); capped it allocates 119 without a
 // vector spill and the fourth workgroup per CU (LDS: 4 x 36 KB) is worth 3 % (toys) to 6 % (dense) of the launch at B = 8192.
@@ -1501,6 +1549,16 @@ static int post_mid_bm(const dr4sr_sasrec_plan* p, const Workspace& ws, const Po
     if (A.xcd) grid.x = xcd_grid((int)grid.x, BM);
     const size_t lds = (BM == 16 && A.at.on) ? sizeof(float) * att_lds_off(p->D, p->F) + att_lds_bytes(p->D)
                        : post_lds(p->D, p->F, BM) + 8 * sizeof(float) + (S.ent ? tile_sort_lds_bytes(BM, 1 << S.logG) : 0);   // + the scorer's (count, loss) reduction scratch + tile_sort's records
+    if constexpr (BM == 16) {
+        if (row_keep_saved(p, ws, A)) {                 // (d = 64, F = 128, training with dropout): the KU forms
+#define PMK(META_, DET_) do { big_lds((k_post_mid<16, 64, 128, META_, DET_, true>), lds); \
+                              hipLaunchKernelGGL((k_post_mid<16, 64, 128, META_, DET_, true>), grid, blk, lds, s, A, S); } while (0)
+            if (S.phi) { if (A.at.kv_part) PMK(true, true); else PMK(true, false); }
+            else { if (A.at.kv_part) PMK(false, true); else PMK(false, false); }
+#undef PMK
+            return DR4SR_LAUNCH_CHECK();
+        }
+    }
 #define PM(D_, F_) do { if (BM == 16 && A.at.kv_part) { big_lds((k_post_mid<BM == 16 ? 16 : 64, D_, F_, false, BM == 16>), lds); \
                                                        hipLaunchKernelGGL((k_post_mid<BM == 16 ? 16 : 64, D_, F_, false, BM == 16>), grid, blk, lds, s, A, S); } \
                         else if constexpr (BM == 32 && D_ == 64) { big_lds(k_post_mid32<D_, F_>, lds); hipLaunchKernelGGL((k_post_mid32<D_, F_>), grid, blk, lds, s, A, S); } \
