@@ -151,6 +151,7 @@ SYMBOLS = {
     "dr4sr_sasrec_plan_sizeof": (C.c_int, []),
     "dr4sr_sasrec_param_layout": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "dr4sr_sasrec_workspace_bytes": (C.c_int64, [_PLANP]),
+    "dr4sr_sasrec_workspace_offsets": (C.c_int, [_PLANP, C.c_int32, C.POINTER(C.c_int64)]),
     "dr4sr_sasrec_at_scale": (C.c_int, [C.c_void_p]),
     "dr4sr_sasrec_fwd_bwd": (C.c_int, [_PLANP, C.c_void_p]),
     "dr4sr_adam_step": (C.c_int, [_PLANP, C.c_void_p]),

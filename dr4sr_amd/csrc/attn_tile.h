@@ -197,6 +197,19 @@ __device__ __forceinline__ Keep own_keep(const PostArgs& P, const int2 mq, const
     }
     return k;
 }
+// KB forms (linear.hip row_keep_saved): the lane's Keep{lo, hi} leaves k_post_fwd as ONE 8-byte word per (token, head) at keep[(t 2 + h) 2]
+// (TileAttnArgs::keep, [T][H][2] words) and k_post_bwd requests it at kernel entry — the address needs t0, the thread index and the head only —
+// instead of running own_keep's two Philox calls behind the token-word load.  Rows >= T hold no word: all ones, as own_keep returns for them.
+__device__ __forceinline__ void keep_store(const TileAttnArgs& A, const Keep k, const int t0, const int T) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, tq = t0 + lane;       // lanes 0..15 (g == 0) of waves 0, 1 (half == 0, h = w)
+    if (w < 2 && lane < 16 && tq < T) *reinterpret_cast<uint2*>(A.keep + ((size_t)tq * 2 + w) * 2) = make_uint2(k.lo, k.hi);
+}
+__device__ __forceinline__ Keep keep_load(const TileAttnArgs& A, const int t0, const int T) {
+    const int tq = t0 + (int)(threadIdx.x & 15), h = (threadIdx.x >> 6) & 1;
+    Keep k{0xffffffffu, 0xffffffffu};
+    if (tq < T) { const uint2 v = *reinterpret_cast<const uint2*>(A.keep + ((size_t)tq * 2 + h) * 2); k.lo = v.x; k.hi = v.y; }
+    return k;
+}
 
 // ------------------------------------------------------------------------------------------------ forward
 // Wave w: head h = w & 1 (scores and softmax of the 16 query rows, computed by both waves of a head), output columns block(s) w >> 1.

@@ -82,14 +82,17 @@ __global__ __launch_bounds__(1024) void k_prep(const PrepArgs P, float* __restri
     }
     __shared__ unsigned long long part[1024];
     prep_body<1024>(P, part);
+    // head of a graph of training steps: the bias corrections of the optimizer launch that follows (no launch moves state[STEP] before it)
+    if (P.bc_rec && threadIdx.x == 64) adam_bc_write(P.bc_rec, P.state[DR4SR_STATE_STEP] + 1, P.lr, P.b1, P.b2);
 }
 
 static int launch_prep_sel(const int64_t* seqlen, const int64_t* rows, int* cu, int* state, int B, int L, int bump_rng, float* zero,
-                           int64_t zero_floats, const PermSel& sel, int* tile_seq, int* seq_class, hipStream_t s) {
+                           int64_t zero_floats, const PermSel& sel, int* tile_seq, int* seq_class, hipStream_t s, const PrepArgs* bc = nullptr) {
     const int64_t n4 = zero ? zero_floats / 4 : 0;
     int zb = (int)((n4 + 1023) / 1024);
     if (zb > 255) zb = 255;
-    const PrepArgs P{seqlen, rows, cu, state, B, L, bump_rng, sel, tile_seq, seq_class, nullptr};
+    const PrepArgs P{seqlen, rows, cu, state, B, L, bump_rng, sel, tile_seq, seq_class, nullptr, bc ? bc->bc_rec : nullptr, bc ? bc->lr : 0.f,
+                     bc ? bc->b1 : 0.f, bc ? bc->b2 : 0.f};
     hipLaunchKernelGGL(k_prep, dim3(1 + zb), dim3(1024), 0, s, P, zero, n4);
     return DR4SR_LAUNCH_CHECK();
 }
@@ -111,15 +114,18 @@ int make_prep_args(const dr4sr_sasrec_plan* p, const Workspace& ws, int bump_rng
     }
     // the length-class lists are only read by the at-scale attention LIST launches (attn_mfma.hip: split_by_length); the wave-per-tile form
     // (attn_wave.hip) needs none of them
-    *out = PrepArgs{p->seqlen, p->rows, ws.cu, p->state, p->B, p->L, bump_rng, sel, ws.tile_seq, (ws.attn_split && !attn_wave_on(p, ws)) ? ws.seq_class : nullptr, ws.len_buf};
+    // the bias-correction record goes with the preps that start a training step under Adam (prep_body.h)
+    int* bc_rec = (bump_rng && p->optimizer == DR4SR_OPT_ADAM && p->workspace) ? ws.bc_rec : nullptr;
+    *out = PrepArgs{p->seqlen, p->rows, ws.cu, p->state, p->B, p->L, bump_rng, sel, ws.tile_seq, (ws.attn_split && !attn_wave_on(p, ws)) ? ws.seq_class : nullptr, ws.len_buf,
+                    bc_rec, p->lr, p->beta1, p->beta2};
     return 0;
 }
-int launch_prep(const dr4sr_sasrec_plan* p, const Workspace& ws, int bump_rng, int zero_grads, hipStream_t s) {
+int launch_prep(const dr4sr_sasrec_plan* p, const Workspace& ws, int bump_rng, int zero_grads, hipStream_t s, int adam_bc) {
     PrepArgs P;
     const int rc = make_prep_args(p, ws, bump_rng, &P);
     if (rc) return rc;
     return launch_prep_sel(p->seqlen, p->rows, ws.cu, p->state, p->B, p->L, bump_rng, zero_grads ? p->grads : nullptr,
-                           ws.n_params + DR4SR_GRAD_TAIL, P.sel, ws.tile_seq, P.seq_class, s);
+                           ws.n_params + DR4SR_GRAD_TAIL, P.sel, ws.tile_seq, P.seq_class, s, adam_bc ? &P : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------

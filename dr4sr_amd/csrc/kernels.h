@@ -13,7 +13,7 @@ struct LayerWs {
     float* qkv;    // [T,3D]  in_proj output (q|k|v)
     float* ctx;    // [T,D]   attention output (heads merged), before out_proj
     float* attn_st; // [T,H,2] softmax row max and 1/row sum per (token, head), saved by the MFMA attention forward
-    unsigned* attn_keep; // [T,H,2] dropout keep bits of (token, head)'s key positions 0..31 | 32..63, saved by the wave-per-tile forward (attn_wave.hip)
+    unsigned* attn_keep; // [T,H,2] dropout keep bits of (token, head)'s key positions 0..31 | 32..63, saved by the wave-per-tile forward (attn_wave.hip) and, in the latency forms, by k_post_fwd<.., KB> for k_post_bwd<.., KB> (attn_tile.h keep_store)
     float* u1;     // [T,D]   x + drop(out_proj(ctx))                     (LayerNorm1 input)
     float* y;      // [T,D]   LayerNorm1 output
     float* st1;    // [T,2]   (mean, rstd) of u1
@@ -39,6 +39,7 @@ struct Workspace {
     bool scale, attn_split;                    // at-scale token-tile forms / length-class attention lists for this plan (see at_scale below)
     bool attn_tile_sa;                         // ... and, for short-sequence plans at d = 64, the window attention of attn_tile.h as launches of its own INSTEAD of the lists (attn_tile_sa.hip)
     int* len_buf;                              // scratch of the two-phase prep (prep_body.h: 16 B per sequence + 16 B per optimizer workgroup)
+    int* bc_rec;                               // Adam's bias-correction record (prep_body.h adam_bc_write): the last 256 bytes of the workspace
     int* seq_class;                            // [4 + 7B] n_short, n_long, n_tiny, - | tiny_desc[B] int4 {t0, n, slot, row} | short_list[B] (9..16) | long_list[B] (> 16) | tiny_list[B] (1..8)  (k_prep)
     float* attn_rd;                            // [Tmax][H] <dctx, ctx> per (token, head): softmax-backward row term, from k_post_bwd
     int* tile_seq;                             // [ceil(Tmax/16)] sequence slot of token 16*i (k_prep), search hint of the token-tile kernels
@@ -113,7 +114,7 @@ __device__ __forceinline__ int xcd_tile(const int T, const int BM, const int on)
 // per-token words {first token of the sequence, sequence slot | sequence length << 20 | PAD << 30} the embedding stage wrote
 struct TileAttnArgs {
     const float* qkv; float* dqkv; float* ctx; float* stat; const int2* tok; int L;
-    unsigned* keep;                            // [T][H][2] dropout keep bits saved by the wave-per-tile forward (attn_wave.hip / wt_attn_ctx) for its backward
+    unsigned* keep;                            // [T][H][2] dropout keep bits saved by the wave-per-tile forward (attn_wave.hip / wt_attn_ctx) for its backward; 16-row tiles: by k_post_fwd<.., KB> for k_post_bwd<.., KB>
     int on;                                    // bit 0: on; bit 1 (DR4SR_ATTN_TILE_ATOMICS): no plain stores for tile-private dK | dV rows; bit 2: near rows first (short-sequence plans)
     // deterministic latency form (Workspace::det_lat): the dK | dV rows a query tile adds to OTHER tiles' tokens (and to shared rows of its own) are
     // stored as this layer's partial blocks [query tile][key tile of the window: 5][16 rows][2 D] instead of added with atomics; the launch that
@@ -241,7 +242,8 @@ int launch_adam_flat(float* P, float* G, float* M, float* V, int64_t n, int* sta
 
 int carve_workspace(const dr4sr_sasrec_plan* p, Workspace* ws);   // fills ws from p->workspace (or sizes only if NULL)
 
-int launch_prep(const dr4sr_sasrec_plan* p, const Workspace& ws, int bump_rng, int zero_grads, hipStream_t s);
+// adam_bc: k_prep also writes the bias-correction record of the optimizer step that follows it (the head of a dr4sr_sasrec_train_steps graph)
+int launch_prep(const dr4sr_sasrec_plan* p, const Workspace& ws, int bump_rng, int zero_grads, hipStream_t s, int adam_bc = 0);
 int make_prep_args(const dr4sr_sasrec_plan* p, const Workspace& ws, int bump_rng, PrepArgs* out);
 int launch_embed_fwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s);
 int launch_embed_bwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s);

@@ -349,13 +349,16 @@ int launch_embqkv_fwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int train
 // Row state that the forward half of k_post_mid<16, 64, ...> hands to its backward half in registers.  ln_rowpass / the GELU pass and
 // ln_bwd_rowpass / the da pass use the SAME thread <-> element map (row = threadIdx.x >> 4, c = 4 * (threadIdx.x & 15) + 64 j), so what
 // the backward row passes would load right behind a barrier (u, (mean, rstd), a) or regenerate (the Philox keep decisions) is what this
-// thread held a few microseconds earlier.  The forward still stores u1 / u2 / st1 / st2 / a (other entry points read them); the carried
-// values equal the stored ones bit for bit.  Keep decisions travel as bits (bit k = element c + k is kept), not as float factors.
+// thread held a few microseconds earlier.  The forward half of k_post_mid does not store u1 / u2 / st1 / st2 / a (no launch reads them: the
+// last layer's k_post_bwd runs only behind a k_post_fwd, which stores them); the carried values equal what it would have stored bit for bit.
+// Keep decisions travel as bits (bit k = element c + k is kept), not as float factors.
 // The same struct serves the layers whose two halves are two launches (k_post_fwd -> k_post_bwd, 16-row tiles at d = 64): the forward stores only
 // the keep decisions, 16 bits per thread (LayerWs::row_keep, row_keep_store below), the backward requests its thread's u2 / st2 / a / u1 /
 // st1 and that word at kernel entry and runs its row passes from registers.
-// Modes (template int CARRY):   forward 0 nothing | 1 everything stays in registers (k_post_mid) | 2 keep bits stored (k_post_fwd<.., KB>)
+// Modes (template int CARRY):   forward 0 nothing | 1 everything stays in registers, nothing of it is stored (k_post_mid) | 2 keep bits stored (k_post_fwd<.., KB>)
 //                               backward 0 loads + Philox inside the passes | 1 registers of the forward half | 2 loads at entry, Philox | 3 loads at entry, saved bits
+// Modes 2 -> 3 also hand over the in-tile attention's keep decisions (attn_tile.h keep_store / keep_load: 8 bytes per (token, head) in
+// LayerWs::attn_keep), so k_post_bwd<.., KB> runs no Philox call at all.
 struct LnCarry { float4 v; float mean, rstd; uint32_t keep; };
 template <int F>
 struct RowCarry { LnCarry ln1, ln2; float4 a[F / 64]; uint32_t akeep; };       // akeep: 4 bits per float4 of the activation dropout
@@ -377,7 +380,8 @@ __device__ __forceinline__ float4 keep_factors4(const RngKey& k, uint32_t bits) 
 //   CARRY (one pass, one float4 per thread): v, (mean, rstd) and the keep bits of this thread's row are left in *cy as well
 //   KPRE (with CARRY): the keep bits ARRIVE in cy->keep (row_keep_word below) — no Philox call here —, and a residual row in global memory
 //   arrives in cy->v (requested at kernel entry)
-template <int BM, int D, bool RES_IN_LDS, bool COPY_LDS, bool CARRY = false, bool KPRE = false>
+//   NOST (with CARRY): U and ST are not stored — the only reader is the backward half of the same launch, from *cy (k_post_mid<16, 64, ...>)
+template <int BM, int D, bool RES_IN_LDS, bool COPY_LDS, bool CARRY = false, bool KPRE = false, bool NOST = false>
 __device__ __forceinline__ void ln_rowpass(const float* __restrict__ Cs, int ldc, const float* res, int ldres,
                                            const float* __restrict__ lnw, const float* __restrict__ lnb, float eps,
                                            float* __restrict__ U, float* __restrict__ OUT, float* __restrict__ ST,
@@ -386,6 +390,7 @@ __device__ __forceinline__ void ln_rowpass(const float* __restrict__ Cs, int ldc
     constexpr int NV = D / 64, PASSES = BM / 16;
     static_assert(!CARRY || (NV == 1 && PASSES == 1), "the carried row state is one float4 per thread");
     static_assert(!KPRE || CARRY, "the keep bits arrive in the carried row state");
+    static_assert(!NOST || CARRY, "the row state leaves through *cy only");
     const int l16 = threadIdx.x & 15, rsub = threadIdx.x >> 4;
     float4 gam[NV], bet[NV], v[PASSES][NV];
     float mean[PASSES], rstd[PASSES];
@@ -410,7 +415,7 @@ __device__ __forceinline__ void ln_rowpass(const float* __restrict__ Cs, int ldc
                 if constexpr (CARRY && !KPRE) cy->keep = keep_bits4(m);
             }
             v[ps][j] = make_float4(r.x + o.x, r.y + o.y, r.z + o.z, r.w + o.w);
-            if (ok) st4(U + (size_t)t * D + c, v[ps][j]);
+            if constexpr (!NOST) { if (ok) st4(U + (size_t)t * D + c, v[ps][j]); }
         }
     }
 #pragma unroll
@@ -430,7 +435,7 @@ __device__ __forceinline__ void ln_rowpass(const float* __restrict__ Cs, int ldc
             if (yreg) yreg[ps][j] = ok ? yv : make_float4(0.f, 0.f, 0.f, 0.f);
             if (COPY_LDS) st4(Ls + row * ldl + c, ok ? yv : make_float4(0.f, 0.f, 0.f, 0.f));
         }
-        if (ok && l16 == 0) { ST[2 * (size_t)t] = mean[ps]; ST[2 * (size_t)t + 1] = rstd[ps]; }
+        if constexpr (!NOST) { if (ok && l16 == 0) { ST[2 * (size_t)t] = mean[ps]; ST[2 * (size_t)t + 1] = rstd[ps]; } }
     }
 }
 
@@ -484,6 +489,9 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
     WFragT<PF ? D : 16, PF ? 3 * D : 64> f_nx;
     STAMP(0);
     static_assert(!KU || (BM == 16 && D == 64 && F == 128 && !FFN_ONLY && CARRY != 0), "one row, one float4, 16 keep bits per thread");
+    // CARRY 1: the backward half of the same launch takes u1 / st1 / a / u2 / st2 from *cy and no other launch reads them (the fused step
+    // runs no k_post_bwd of this layer; k_wgrad reads y, h, ctx, x) — they are not stored, and A holds null pointers for them
+    constexpr bool NOST = CARRY == 1;
     auto keep_upfront = [&]() {
         if constexpr (KU) {
             const uint32_t w = row_keep_word(rk, sP, sF, sA, actdrop, t0 + rsub);
@@ -528,6 +536,7 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
                 __builtin_amdgcn_sched_barrier(0);
                 const tattn::Keep k = tattn::fwd_compute<D, KEEPQ>(A, t0, T, R0, LD, smem + att_lds_off(D, F), att_pre);
                 if (keep_out) *keep_out = k;
+                if constexpr (CARRY == 2) tattn::keep_store(A.at, k, t0, T);        // for k_post_bwd<.., KB>
                 __builtin_amdgcn_sched_barrier(0);
                 if (A.nx_qkv) { if constexpr (D == 128) wfrag_load_img(f_nx, reinterpret_cast<const float*>(A.sp) + WSplitGeo<D, F>::E); else wfrag_load(f_nx, A.nx_in_w, D); }
             } else {
@@ -552,6 +561,7 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
                     tattn::fwd_stage<D, KEEPQ>(A, t0, T, smem + att_lds_off(D, F), att_pre);
                     const tattn::Keep k = tattn::fwd_compute<D, KEEPQ>(A, t0, T, R0, LD, smem + att_lds_off(D, F), att_pre);
                     if (keep_out) *keep_out = k;
+                    if constexpr (CARRY == 2) tattn::keep_store(A.at, k, t0, T);
                 }
             }
         }
@@ -566,7 +576,7 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
         lds_barrier(); STAMP(2);
         if constexpr (KU && !KU_EARLY) keep_upfront();
         // ---- dropout1 + residual + LayerNorm1
-        ln_rowpass<BM, D, false, true, CARRY != 0, KU>(R2, LD, A.x, D, A.ln1_w, A.ln1_b, A.eps, A.u1, A.y, A.st1, R1, LD, t0, T, dodrop, rk, sP, nullptr,
+        ln_rowpass<BM, D, false, true, CARRY != 0, KU, NOST>(R2, LD, A.x, D, A.ln1_w, A.ln1_b, A.eps, A.u1, A.y, A.st1, R1, LD, t0, T, dodrop, rk, sP, nullptr,
                                                   CARRY ? &cy->ln1 : nullptr);
     }
     lds_barrier(); STAMP(3);
@@ -601,7 +611,7 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
                     h.x *= m.x; h.y *= m.y; h.z *= m.z; h.w *= m.w;
                     if constexpr (CARRY != 0 && !KU) cy->akeep |= keep_bits4(m) << (4 * j);
                 }
-                if (ok) { st4(A.a + (size_t)t * F + c, a4); st4(A.h + (size_t)t * F + c, h); }
+                if (ok) { if constexpr (!NOST) st4(A.a + (size_t)t * F + c, a4); st4(A.h + (size_t)t * F + c, h); }
                 st4(R2 + row * LF + c, h);
             }
         }
@@ -617,7 +627,7 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
     }
     lds_barrier(); STAMP(6);
     if (!FFN_ONLY && A.nx_qkv) {               // layer-boundary fusion: keep z in LDS and emit the next layer's in_proj
-        ln_rowpass<BM, D, true, true, CARRY != 0, KU>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, R1, LD, t0, T, dodrop, rk, sF, nullptr,
+        ln_rowpass<BM, D, true, true, CARRY != 0, KU, NOST>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, R1, LD, t0, T, dodrop, rk, sF, nullptr,
                                                   CARRY ? &cy->ln2 : nullptr);
         if constexpr (CARRY == 2) row_keep_store<F>(A, *cy, t0, T);
         lds_barrier();
@@ -628,7 +638,7 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
         tile_to_global<BM, 3 * D>(acc, A.nx_qkv, 3 * D, A.nx_in_b, t0, T);
         if (A.nx_dqkv_zero) zero_kv_rows<BM, D>(A.nx_dqkv_zero, t0, T);
     } else {
-        ln_rowpass<BM, D, true, false, CARRY != 0, KU>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, nullptr, 0, t0, T, dodrop, rk, sF, zreg,
+        ln_rowpass<BM, D, true, false, CARRY != 0, KU, NOST>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, nullptr, 0, t0, T, dodrop, rk, sF, zreg,
                                                    CARRY ? &cy->ln2 : nullptr);
         if constexpr (CARRY == 2) row_keep_store<F>(A, *cy, t0, T);
     }
@@ -824,15 +834,21 @@ __device__ __forceinline__ void post_bwd_body(const PostArgs& A, const int t0, c
             if constexpr (CARRY == 3) {
                 const uint32_t w = ok ? (uint32_t)A.row_keep[16 * (size_t)t + l16] : 0u;
                 cy_ld.ln1.keep = w & 15u; cy_ld.ln2.keep = (w >> 4) & 15u; cy_ld.akeep = w >> 8;
+                if (at_stage) keep = tattn::keep_load(A.at, t0, T);     // the attention's keep decisions as k_post_fwd<.., KB> held them: no Philox call below
             }
             __builtin_amdgcn_sched_barrier(0);
         }
         if (at_stage) {
-            const int2 mq = tattn::own_word(A.at, t0, T);
-            att_st.issue(A.at, t0, T, (A.at.on & 4) ? tattn::NEAR0 : 0, tattn::WR);
-            __builtin_amdgcn_sched_barrier(0);
-            keep = tattn::own_keep(A, mq, t0, T);          // Philox calls while the window is in flight
-            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (CARRY == 3) {                    // (the window's rows carry the token words bwd() reads from LDS)
+                att_st.issue(A.at, t0, T, (A.at.on & 4) ? tattn::NEAR0 : 0, tattn::WR);
+                __builtin_amdgcn_sched_barrier(0);
+            } else {
+                const int2 mq = tattn::own_word(A.at, t0, T);
+                att_st.issue(A.at, t0, T, (A.at.on & 4) ? tattn::NEAR0 : 0, tattn::WR);
+                __builtin_amdgcn_sched_barrier(0);
+                keep = tattn::own_keep(A, mq, t0, T);      // Philox calls while the window is in flight
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
     }
     STAMP(16);
@@ -1435,6 +1451,7 @@ __device__ __forceinline__ void post_mid_body(const PostArgs& A, const ScoreTile
         if (!S.rec) Af.z = nullptr;                          // the query rows leave the kernel only when the owner job will gather them
         tattn::Keep keep{0xffffffffu, 0xffffffffu};
         constexpr int CARRY = BM == 16 ? 1 : 0;              // latency regime: the row passes' state crosses the two halves in registers
+        if constexpr (CARRY == 1) Af.u1 = Af.st1 = Af.a = Af.u2 = Af.st2 = nullptr;      // ... and nowhere else: the forward half does not store it
         RowCarry<F> cy;
         post_fwd_body<BM, D, F, false, true, CARRY, KU>(Af, t0, T, zreg, &keep, &cy);
         if constexpr (BM != 16) score_prefetch<BM>(A, S, t0, T, P);             // occupancy regime: its registers would cost a workgroup per CU

@@ -11,7 +11,33 @@ struct PermSel { const int64_t* perm; int64_t n, stride, offset; int* counter; }
 struct PrepArgs {
     const int64_t* seqlen; const int64_t* rows; int* cu; int* state; int B, L, bump_rng; PermSel sel; int* tile_seq; int* seq_class;
     int* len_buf;                              // scratch of the two-phase form (prep_phase1 -> prep_phase2: 4 B + 4 PREP_MAX_BLK words), or NULL
+    int* bc_rec;                               // Adam's bias-correction record of the step being prepared (adam_bc_write below), or NULL: none kept
+    float lr, b1, b2;                          // ... and the rest of its key (the step number comes from state[STEP])
 };
+
+// Adam's bias corrections, cached one step ahead.  k_adam used to evaluate two fp64 pow() in thread 0 of every workgroup, in front of a barrier
+// its first loads waited behind (~1 us of the B = 256 step).  Whoever prepares step t — the prep workgroup of the previous optimizer launch, or
+// the k_prep at the head of a graph — evaluates the SAME double expressions beside its own work and leaves
+//   {t, bits of lr, b1, b2, step_size = (float)(lr / (1 - b1^t)), inv_sqrt_bc2 = (float)(1 / sqrt(1 - b2^t))}
+// in slot t & 1 of the record: 2 slots x DR4SR_BC_SLOT_WORDS words, the last 256 bytes of the plan's workspace.  k_adam<ADAM, BC> takes the pair
+// when the slot's key equals its own (t, lr, b1, b2) bit for bit and evaluates the expressions itself otherwise (first step, changed learning
+// rate, a record of another workspace: the pair is a pure function of the key, so ANY record with the right key holds the right pair).
+// Two slots: the prep workgroup writes slot (t + 1) & 1 while the other workgroups of the same launch read slot t & 1.  On a poisoned step it
+// rewrites slot t & 1 itself (the step counter does not move); the readers of that launch update nothing, so what they read does not matter.
+#define DR4SR_BC_SLOT_WORDS 8
+__device__ __forceinline__ void adam_bias_terms(const float lr, const float b1, const float b2, const int t, float& step_size, float& inv_sqrt_bc2) {
+    const double bc1 = 1.0 - pow((double)b1, (double)t), bc2 = 1.0 - pow((double)b2, (double)t);
+    step_size = (float)((double)lr / bc1);
+    inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+}
+// one thread
+__device__ __forceinline__ void adam_bc_write(int* rec, const int t, const float lr, const float b1, const float b2) {
+    float step_size, inv_sqrt_bc2;
+    adam_bias_terms(lr, b1, b2, t, step_size, inv_sqrt_bc2);
+    int* r = rec + DR4SR_BC_SLOT_WORDS * (t & 1);
+    *reinterpret_cast<int4*>(r) = make_int4(t, __float_as_int(lr), __float_as_int(b1), __float_as_int(b2));
+    *reinterpret_cast<int2*>(r + 4) = make_int2(__float_as_int(step_size), __float_as_int(inv_sqrt_bc2));
+}
 
 // Two-phase form for large batches (the optimizer launch prepares the next step; one workgroup doing 8 192 sequences by itself was
 // 41 us as a launch of its own, and 25 us as the serial tail of the optimizer launch when only the selection was spread out).
@@ -88,9 +114,12 @@ __device__ __forceinline__ void prep_phase1(const PrepArgs& P, const int blk, co
 // wg / nwg: the per-sequence part is strided over nwg workgroups (k_prep_phase2: a launch of its own spread over the device — as the tail
 // of the optimizer launch, on ONE workgroup, it was 22 us of a B = 8 192 step and 68 us of a B = 32 768 step: one CU's scattered-store
 // rate); every workgroup repeats the (cheap) scan of the <= 1 024 totals, workgroup 0 writes the scalars.
-template <int NT>
+// t_next: the optimizer step being prepared when the caller is the optimizer launch itself (its ticket has just moved state[STEP]); < 0: a
+// launch of its own behind it, which reads state[STEP].  BCW: this caller writes Adam's bias-correction record (the forms that do not are
+// the code they were)
+template <int NT, bool BCW = false>
 __device__ __forceinline__ void prep_phase2(const PrepArgs& P, const int nblk, unsigned long long* part, int4* boff, const int wg = 0,
-                                            const int nwg = 1) {
+                                            const int nwg = 1, const int t_next = -1) {
     const int B = P.B, C = (B + nblk - 1) / nblk;
     const unsigned long long* pre = reinterpret_cast<const unsigned long long*>(P.len_buf);
     int* __restrict__ cu = P.cu; int* __restrict__ tile_seq = P.tile_seq; int* __restrict__ seq_class = P.seq_class;
@@ -142,6 +171,7 @@ __device__ __forceinline__ void prep_phase2(const PrepArgs& P, const int nblk, u
         }
     }
     if (wg != 0) return;
+    if constexpr (BCW) { if (threadIdx.x == 64) adam_bc_write(P.bc_rec, t_next >= 0 ? t_next : P.state[DR4SR_STATE_STEP] + 1, P.lr, P.b1, P.b2); }
     if (P.sel.perm && threadIdx.x == 0) *P.sel.counter = *P.sel.counter + 1;       // every reader of the counter is past its launch's ticket
     if (threadIdx.x == NT - 1) {
         const int T = (int)(carry & 0xffffffffull);

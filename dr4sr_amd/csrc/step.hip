@@ -244,6 +244,8 @@ int carve_workspace(const dr4sr_sasrec_plan* p, Workspace* ws) {
     // row-pass keep bits of the latency-regime tile kernels (LayerWs::row_keep, 32 B per token slot and layer).  For EVERY workspace — the plans
     // that share one differ in regime — and LAST: nothing carved above moves
     for (int l = 0; l < p->n_layer; ++l) ws->layer[l].row_keep = reinterpret_cast<unsigned short*>(take(Tmax * 8));
+    // Adam's bias-correction record (prep_body.h: 2 slots x DR4SR_BC_SLOT_WORDS words): the LAST 256 bytes of every workspace
+    ws->bc_rec = (int*)take(2 * DR4SR_BC_SLOT_WORDS);
     ws->bytes = o;
     return 0;
 }
@@ -257,6 +259,23 @@ extern "C" int64_t dr4sr_sasrec_workspace_bytes(const dr4sr_sasrec_plan* plan) {
     Workspace ws;
     carve_workspace(&q, &ws);
     return ws.bytes;
+}
+
+// Layout query (include/dr4sr_hip.h): where carve_workspace puts the buffers a test prefills or reads back, for THIS plan under the
+// switches in force (deterministic mode carves more in front of the layers) — byte offsets from plan->workspace.
+extern "C" int dr4sr_sasrec_workspace_offsets(const dr4sr_sasrec_plan* plan, int32_t layer, int64_t* out) {
+    if (!plan || !out) return DR4SR_E_ARG;
+    dr4sr_sasrec_plan q = *plan;
+    if (q.B <= 0 || q.L <= 0 || q.n_layer <= 0 || q.n_layer > DR4SR_MAX_LAYERS || layer < 0 || layer >= q.n_layer) return DR4SR_E_ARG;
+    if (check_shape(&q)) return DR4SR_E_SHAPE;
+    char* const base = reinterpret_cast<char*>(uintptr_t(1) << 20);      // never dereferenced: carve_workspace only adds to it
+    q.workspace = base;
+    Workspace ws;
+    carve_workspace(&q, &ws);
+    const LayerWs& w = ws.layer[layer];
+    const void* const p[DR4SR_WS_OFF_COUNT] = {w.attn_keep, w.u1, w.st1, w.a, w.u2, w.st2, w.row_keep, ws.bc_rec};
+    for (int i = 0; i < DR4SR_WS_OFF_COUNT; ++i) out[i] = (int64_t)(reinterpret_cast<const char*>(p[i]) - base);
+    return 0;
 }
 
 extern "C" int dr4sr_sasrec_at_scale(const dr4sr_sasrec_plan* plan) {
@@ -305,8 +324,13 @@ static int get_ws(const dr4sr_sasrec_plan* p, Workspace* ws) {
 //   DR4SR_OPT_ADAGRAD  torch.optim.Adagrad(lr, weight_decay)    g += wd p ; V += g^2 ; p -= lr g / (sqrt(V) + eps)     (eps 1e-10, lr_decay 0)
 //   DR4SR_OPT_RMSPROP  torch.optim.RMSprop(lr, weight_decay)    g += wd p ; V = b2 V + (1 - b2) g^2 ; p -= lr g / (sqrt(V) + eps)   (b2 = alpha 0.99)
 // The un-normalised gradient, the poison word, the step counter and the fused next-step prep are the same for all four.
+// BC (host: OPT = ADAM and a `next` that keeps a bias-correction record, prep_body.h): the corrections of THIS step are taken from the record
+// — every thread reads both slots at entry, beside state[STEP] and the gradient tail; no pow(), no LDS hand-off, no barrier in front of the
+// sweep — and the prep (extra workgroup | k_prep_phase2 | the last workgroup) writes the record of the next step.  A slot whose key differs
+// from (t, lr, b1, b2) is ignored and the thread evaluates the expressions itself.  Every other launch (the eager dr4sr_adam_step, the last
+// step of a graph, the flat entry point without a prep, the other optimizers) is the BC = false form: corrections inline, as before.
 struct AdamNext { int enable; int phase2_launch; PrepArgs prep; };
-template <int OPT>
+template <int OPT, bool BC = false>
 __global__ __launch_bounds__(256) void k_adam(float* __restrict__ P, float* __restrict__ G, float* __restrict__ M,
                                               float* __restrict__ V, int64_t n, int* __restrict__ state, float lr, float b1,
                                               float b2, float eps, float wd, float* __restrict__ loss_log,
@@ -315,6 +339,12 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ P, float* __re
     __shared__ unsigned long long part[256];
     __shared__ int4 boff[PREP_MAX_BLK];            // two-phase prep: token / class offsets of the workgroups' sequence ranges
     const int t = state[DR4SR_STATE_STEP] + 1;
+    int4 bk0, bk1; int2 bv0, bv1;                          // BC: both slots of the record (their addresses do not depend on t)
+    if constexpr (BC) {
+        const int* rec = next.prep.bc_rec;
+        bk0 = *reinterpret_cast<const int4*>(rec); bv0 = *reinterpret_cast<const int2*>(rec + 4);
+        bk1 = *reinterpret_cast<const int4*>(rec + DR4SR_BC_SLOT_WORDS); bv1 = *reinterpret_cast<const int2*>(rec + DR4SR_BC_SLOT_WORDS + 4);
+    }
     const float nvalid = G[n];
     const float gs = nvalid > 0.f ? 1.0f / nvalid : 0.f;
     const bool poisoned = G[n + 2] != 0.f;
@@ -328,14 +358,26 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ P, float* __re
         if (loss_log && threadIdx.x == 0) loss_log[log_index ? max(*log_index - 1, 0) : 0] = lossv;
         __syncthreads();
         prep_body<256>(next.prep, part);
+        // the next optimizer step's bias corrections, beside the sweep (wave 1: waves 0 and 3 hold prep_body's tail).  t and `poisoned` were read
+        // at entry like everywhere else, before the ticket moves them: the next step is t + 1, or t again when this one is skipped
+        if constexpr (BC) { if (threadIdx.x == 64) adam_bc_write(next.prep.bc_rec, poisoned ? t : t + 1, lr, b1, b2); }
     } else {
-        if (threadIdx.x == 0) {               // double-precision bias corrections, once per block
-            const double bc1 = 1.0 - pow((double)b1, (double)t), bc2 = 1.0 - pow((double)b2, (double)t);
-            sh[0] = (float)((double)lr / bc1);
-            sh[1] = (float)(1.0 / sqrt(bc2));
+        float step_size, inv_sqrt_bc2;
+        if constexpr (BC) {
+            const int4 bk = (t & 1) ? bk1 : bk0;
+            const int2 bv = (t & 1) ? bv1 : bv0;
+            if (bk.x == t && bk.y == __float_as_int(lr) && bk.z == __float_as_int(b1) && bk.w == __float_as_int(b2)) {
+                step_size = __int_as_float(bv.x); inv_sqrt_bc2 = __int_as_float(bv.y);
+            } else adam_bias_terms(lr, b1, b2, t, step_size, inv_sqrt_bc2);      // (per thread, no barrier: waves of a skipped step may disagree on the slot)
+        } else {
+            if (threadIdx.x == 0) {               // double-precision bias corrections, once per block
+                const double bc1 = 1.0 - pow((double)b1, (double)t), bc2 = 1.0 - pow((double)b2, (double)t);
+                sh[0] = (float)((double)lr / bc1);
+                sh[1] = (float)(1.0 / sqrt(bc2));
+            }
+            __syncthreads();
+            step_size = sh[0]; inv_sqrt_bc2 = sh[1];
         }
-        __syncthreads();
-        const float step_size = sh[0], inv_sqrt_bc2 = sh[1];
         if (!next.enable && loss_log && blk == 0 && threadIdx.x == 0) loss_log[log_index ? max(*log_index - 1, 0) : 0] = G[n + 1] * gs;
         const int64_t n4 = n / 4;
         auto upd = [&](float& pe, float& me, float& ve, float ge) {
@@ -399,7 +441,7 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ P, float* __re
     }
     if (next.enable == 2 && !next.phase2_launch) {   // two-phase prep, phase 2: by the last workgroup, from agent-scope loads of what phase 1 published
         __syncthreads();                       // (run right after phase 1 instead, behind an agent-scope fence and a ticket of its own, the
-        if (s_last) prep_phase2<256>(next.prep, (int)gridDim.x, part, boff);     //  launch got longer: 32 -> 43 us at B = 8 192)
+        if (s_last) prep_phase2<256, BC>(next.prep, (int)gridDim.x, part, boff, 0, 1, poisoned ? t : t + 1);     //  launch got longer: 32 -> 43 us at B = 8 192)
     }
 }
 
@@ -408,6 +450,12 @@ __global__ __launch_bounds__(256) void k_prep_phase2(const PrepArgs P, const int
     __shared__ unsigned long long part[256];
     __shared__ int4 boff[PREP_MAX_BLK];
     prep_phase2<256>(P, nblk, part, boff, (int)blockIdx.x, (int)gridDim.x);
+}
+// ... behind k_adam<ADAM, BC>: workgroup 0 also writes the bias-correction record of the step it prepares
+__global__ __launch_bounds__(256) void k_prep_phase2_bc(const PrepArgs P, const int nblk) {
+    __shared__ unsigned long long part[256];
+    __shared__ int4 boff[PREP_MAX_BLK];
+    prep_phase2<256, true>(P, nblk, part, boff, (int)blockIdx.x, (int)gridDim.x);
 }
 
 int launch_adam_flat(float* P, float* G, float* M, float* V, int64_t n, int* state, float lr, float b1, float b2,
@@ -419,7 +467,9 @@ int launch_adam_flat(float* P, float* G, float* M, float* V, int64_t n, int* sta
     AdamNext nx;
     nx.enable = next ? (next->B > 1024 && next->len_buf && blocks <= PREP_MAX_BLK && (next->B + blocks - 1) / blocks < 65536 ? 2 : 1) : 0;
     nx.phase2_launch = 0;
-    if (next) nx.prep = *next; else nx.prep = PrepArgs{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, PermSel{nullptr, 0, 0, 0, nullptr}, nullptr, nullptr, nullptr};
+    if (next) nx.prep = *next; else nx.prep = PrepArgs{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, PermSel{nullptr, 0, 0, 0, nullptr}, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f};
+    if (opt != DR4SR_OPT_ADAM) nx.prep.bc_rec = nullptr;                    // the record is Adam's
+    else if (nx.prep.bc_rec) { nx.prep.lr = lr; nx.prep.b1 = b1; nx.prep.b2 = b2; }     // ... keyed by THIS launch's hyper-parameters
     const bool p2_inline = DR4SR_ENV("DR4SR_PREP2_INLINE") != nullptr;      // cross-check: phase 2 as the tail of the optimizer launch
     nx.phase2_launch = nx.enable == 2 && !p2_inline;
     const dim3 grid((unsigned)blocks + (nx.enable == 1 ? 1 : 0));
@@ -427,13 +477,17 @@ int launch_adam_flat(float* P, float* G, float* M, float* V, int64_t n, int* sta
         case DR4SR_OPT_SGD: hipLaunchKernelGGL(k_adam<DR4SR_OPT_SGD>, grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx); break;
         case DR4SR_OPT_ADAGRAD: hipLaunchKernelGGL(k_adam<DR4SR_OPT_ADAGRAD>, grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx); break;
         case DR4SR_OPT_RMSPROP: hipLaunchKernelGGL(k_adam<DR4SR_OPT_RMSPROP>, grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx); break;
-        default: hipLaunchKernelGGL(k_adam<DR4SR_OPT_ADAM>, grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx);
+        default:
+            // the form that reads (and whose prep writes) the bias-correction record: where the prep keeps one (SASRec plans; prep_body.h)
+            if (next && next->bc_rec) hipLaunchKernelGGL((k_adam<DR4SR_OPT_ADAM, true>), grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx);
+            else hipLaunchKernelGGL(k_adam<DR4SR_OPT_ADAM>, grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx);
     }
     if (nx.phase2_launch) {
         const int B = next->B, per = 8 * 256;
         int g2 = (B + per - 1) / per;
         if (g2 > 256) g2 = 256;
-        hipLaunchKernelGGL(k_prep_phase2, dim3(g2), dim3(256), 0, s, nx.prep, (int)blocks);
+        if (nx.prep.bc_rec) hipLaunchKernelGGL(k_prep_phase2_bc, dim3(g2), dim3(256), 0, s, nx.prep, (int)blocks);
+        else hipLaunchKernelGGL(k_prep_phase2, dim3(g2), dim3(256), 0, s, nx.prep, (int)blocks);
     }
     return DR4SR_LAUNCH_CHECK();
 }
@@ -647,7 +701,7 @@ extern "C" int dr4sr_sasrec_train_steps(const dr4sr_sasrec_plan* plan, int32_t n
     hipStream_t s = (hipStream_t)stream;
     PrepArgs next;
     RC(make_prep_args(plan, ws, 1, &next));
-    RC(launch_prep(plan, ws, 1, 1, s));
+    RC(launch_prep(plan, ws, 1, 1, s, 1));                 // ... and the first optimizer launch's bias-correction record
     for (int i = 0; i < n_steps; ++i) {
         RC(fwd_bwd_core(plan, ws, s));
         const bool last = i == n_steps - 1;
@@ -681,6 +735,9 @@ extern "C" int dr4sr_sasrec_encode_bwd(const dr4sr_sasrec_plan* plan, int32_t tr
 // ------------------------------------------------------------------------------------------------
 // Measurement hook (bench.py / profiles): enqueue ONE kernel of the step so that its launch duration can
 // be bracketed with HIP events on the caller's stream.  Uses whatever the last fwd_bwd left in the workspace.
+// After a FUSED step that is not everything DR4SR_K_POST_BWD of the LAST layer reads: k_post_mid<16, 64, ...> (latency forms, d = 64) keeps
+// that layer's u1 / st1 / a / u2 / st2 in registers and never stores them, so the launch then runs on whatever the buffers held before
+// (its duration is the same; its output is not a gradient).  Run DR4SR_K_POST_FWD of that layer first where the values matter.
 extern "C" int dr4sr_sasrec_launch_kernel(const dr4sr_sasrec_plan* plan, int32_t kernel, int32_t layer, void* stream) {
     return dr4sr_sasrec_launch_kernel_weighted(plan, nullptr, kernel, layer, stream);
 }

@@ -131,6 +131,20 @@ int64_t dr4sr_sasrec_param_layout(int32_t n_items, int32_t L, int32_t D, int32_t
  * encoder shape without kernels — L > 64; (D, F) outside {(64,128), (64,256), (128,128)}; head_dim other than 32 / 64; a head count != 2
  * whose one-wave-per-head attention would not fit 160 KB of LDS — so an unsupported configuration is refused when the engine is built. */
 int64_t dr4sr_sasrec_workspace_bytes(const dr4sr_sasrec_plan* plan);
+/* Byte offsets, from plan->workspace, of buffers of `layer` inside that scratch (plan->workspace itself may be NULL): the layout depends
+ * on the plan's B and on the switches in force (deterministic mode), so whoever prefills or reads a buffer back — the tests — asks for it.
+ * out[DR4SR_WS_OFF_COUNT]: attn_keep [T][H][2] words | u1 [T][D] | st1 [T][2] | a [T][F] | u2 [T][D] | st2 [T][2] floats |
+ * row_keep [T][16] half-words | Adam's bias-correction record (2 slots x 8 words, not per layer), with T = B * L. */
+#define DR4SR_WS_OFF_ATTN_KEEP 0
+#define DR4SR_WS_OFF_U1        1
+#define DR4SR_WS_OFF_ST1       2
+#define DR4SR_WS_OFF_A         3
+#define DR4SR_WS_OFF_U2        4
+#define DR4SR_WS_OFF_ST2       5
+#define DR4SR_WS_OFF_ROW_KEEP  6
+#define DR4SR_WS_OFF_BC_REC    7
+#define DR4SR_WS_OFF_COUNT     8
+int dr4sr_sasrec_workspace_offsets(const dr4sr_sasrec_plan* plan, int32_t layer, int64_t* out);
 /* launch forms a step of this plan takes (see expected_tokens): bit 0 = at-scale token-tile kernels (32-row tiles, scatter / owner jobs),
  * bit 1 = the at-scale attention regime of short-sequence plans (length-class lists, or — bit 4 — the wave-per-tile launches that
  * replace them: csrc/attn_wave.hip), bit 2 = the attention runs inside the 16-token tile launches (the latency forms: no attention
