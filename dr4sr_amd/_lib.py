@@ -20,6 +20,8 @@ STATE_STEP, STATE_T, STATE_NVALID, STATE_RNGSTEP = 0, 1, 2, 3
 POOL_NONE, POOL_ORIGIN, POOL_LAST, POOL_MEAN = 0, 1, 2, 3
 SITE_EMB, SITE_ATTN, SITE_PROJ, SITE_ACT, SITE_FFN = 0, 1, 2, 3, 4
 OPT_ADAM, OPT_SGD, OPT_ADAGRAD, OPT_RMSPROP = 0, 1, 2, 3        # DR4SR_OPT_* (include/dr4sr_hip.h)
+RANK_NONE = 2 ** 31 - 1       # DR4SR_RANK_NONE: dr4sr_target_rank's answer for a row whose target is not a valid item
+RANK_METRICS = ("ndcg", "recall", "precision", "map", "mrr", "hit", "f1")      # slot order of dr4sr_rank_metrics_accumulate
 
 
 def check_ids(idx, n_items: int, what: str = "index"):
@@ -310,6 +312,12 @@ SYMBOLS = {
     "dr4sr_gnn_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
     "dr4sr_gnn_propagate": (C.c_int, [_i64p, C.c_void_p, _f32p, C.c_int32, C.c_int32, C.c_int32, _f32p, _f32p, C.c_int32, C.c_void_p, C.c_int64,
                                       C.c_void_p]),
+    # additive to ABI 10: evaluation by target rank + metric sums on the device (csrc/rank.hip)
+    "dr4sr_target_rank_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "dr4sr_target_rank": (C.c_int, [_f32p, _f32p, _i64p, _i64p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                    C.c_int64, C.c_void_p]),
+    "dr4sr_rank_metrics_accumulate": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p,
+                                                C.c_void_p]),
     "dr4sr_crash_line_set": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32]),           # measurement hook (include/dr4sr_hip_hooks.h)
 }
 

@@ -675,11 +675,55 @@ class BaseModel(nn.Module):
     # ------------------------------------------------------------------------------------------ eval
     @torch.no_grad()
     def validation_epoch(self, nepoch, dataloader):
+        if self.config["eval"].get("rank_eval", False):
+            return self._rank_epoch(dataloader, self.config["eval"]["val_metrics"], [self.config["eval"]["cutoff"][0]])
         return [self.validation_step(batch) for batch in dataloader]
 
     @torch.no_grad()
     def test_epoch(self, dataloader):
+        if self.config["eval"].get("rank_eval", False):
+            return self._rank_epoch(dataloader, self.config["eval"]["test_metrics"], self.config["eval"]["cutoff"])
         return [self.test_step(batch) for batch in dataloader]
+
+    def _rank_epoch(self, dataloader, metric, cutoffs):
+        """eval.rank_eval: a whole split by target rank.  Per batch forward(), dr4sr_target_rank (the top-k's GEMM with a
+        compare-and-count epilogue: no score matrix, no selection) and dr4sr_rank_metrics_accumulate (fp64 sums on the device); ONE
+        device-to-host copy per split.  -> [({name@c: 0-dim float64 tensor}, rows)], the shape _epoch_end takes.  Same members as
+        topk(): self.engine, self.item_embedding, self.forward."""
+        names = [m for m, _ in evaluation.get_rank_metrics(metric)]
+        assert len(names) > 0
+        cutoffs = [int(c) for c in (cutoffs if isinstance(cutoffs, list) else [cutoffs])]
+        k = int(self.config["eval"]["topk"])
+        for c in cutoffs:
+            if not 1 <= c <= k:
+                raise ValueError(f"eval.rank_eval: eval.cutoff {c} must lie in [1, eval.topk = {k}]")
+        slots = len(_lib.RANK_METRICS)
+        eng, lib = self.engine, self.engine.lib
+        blocked = self._domain_blocked(self.eval_domain)
+        E = self.item_embedding.weight
+        acc = torch.zeros(1 + slots * len(cutoffs), dtype=torch.float64, device=E.device)
+        cuts = (C.c_int32 * len(cutoffs))(*cutoffs)
+        for batch in dataloader:
+            query = self.forward(batch).contiguous()
+            B = query.shape[0]
+            target = batch[self.fiid].reshape(-1).to(torch.int64).contiguous()
+            label = batch["label"].reshape(-1).to(torch.float32).contiguous()
+            hist = batch["user_hist"].contiguous()
+            need = int(lib.dr4sr_target_rank_workspace_bytes(B))
+            ws = getattr(self, "_rank_ws", None)
+            if ws is None or ws.numel() * 4 < need + 4 * B:        # [the call's workspace | rank int32 [B]]
+                ws = self._rank_ws = torch.empty(need // 4 + B, dtype=torch.int32, device=query.device)
+            rank = ws[need // 4:need // 4 + B]
+            _lib.check(lib.dr4sr_target_rank(_lib.ptr(query), _lib.ptr(E), _lib.ptr(target), _lib.ptr(hist), _lib.ptr(blocked),
+                                             _lib.ptr(rank), B, eng.D, self.num_items, hist.shape[1], _lib.ptr(ws), need,
+                                             _lib.cur_stream()), "target_rank")
+            _lib.check(lib.dr4sr_rank_metrics_accumulate(_lib.ptr(rank), _lib.ptr(label), B, cuts, len(cutoffs), k, _lib.ptr(acc),
+                                                         _lib.cur_stream()), "rank_metrics_accumulate")
+        host = acc.cpu()                                       # the split's one device-to-host copy
+        rows = int(host[0])
+        out = {f"{name}@{c}": host[1 + slots * ci + _lib.RANK_METRICS.index(name)] / max(rows, 1)
+               for ci, c in enumerate(cutoffs) for name in names}
+        return [(out, rows)]
 
     def _epoch_end(self, outputs, metric_names):
         metric_list, bs = zip(*outputs)

@@ -12,6 +12,7 @@ a reference-style model written against plain torch ops:
     loss_from_scores(pos, neg, kind) -> (loss_pos, stats)     model/loss_func.py on score tensors (autograd: d pos, d neg)
     neg_sample(n, n_items, seed, step) -> ids                 model/basemodel.py:50-61
     full_score_topk(q, E, hist, item_blocked, k) -> (score, ids)   model/basemodel.py:354-365
+    target_rank(q, E, target, hist, item_blocked) -> rank int32 [B]   the target's position in that top-k order, without the top-k
     fused_adam_(params, grads, m, v, state, lr, b1, b2, eps, wd)   torch.optim.Adam on flat buffers (in place)
 
 Every implementation only enqueues HIP kernels of libdr4sr_hip.so on the current stream; there is no CPU kernel (the ops raise on
@@ -216,7 +217,32 @@ def _(q, E, hist, item_blocked, k):
     return q.new_empty(q.shape[0], k), q.new_empty(q.shape[0], k, dtype=torch.int64)
 
 
-@torch.library.custom_op(f"{NS}::fused_adam_", mutates_args=("params", "adam_m", "adam_v", "state"))
+@torch.library.custom_op(f"{NS}::target_rank", mutates_args=())
+def target_rank(q: torch.Tensor, E: torch.Tensor, target: torch.Tensor, hist: Optional[torch.Tensor],
+                item_blocked: Optional[torch.Tensor]) -> torch.Tensor:
+    """int32 [B]: how many valid items precede target[b] in (score descending, id ascending) order; _lib.RANK_NONE for a target that
+    is not a valid item (PAD, out of range, blocked, in the row's own history)"""
+    _need_cuda(q, E, target, hist, item_blocked)
+    lib = _lib.load()
+    B, D = q.shape
+    N = int(E.shape[0])
+    qc, Ec, tc = q.contiguous(), E.contiguous(), target.contiguous().view(-1)
+    hc = hist.contiguous() if hist is not None else None
+    bc = item_blocked.contiguous() if item_blocked is not None else None
+    rank = torch.empty(B, dtype=torch.int32, device=q.device)
+    nb = int(lib.dr4sr_target_rank_workspace_bytes(B))
+    ws = torch.empty(max(nb // 4, 1), dtype=torch.float32, device=q.device)
+    _lib.check(lib.dr4sr_target_rank(_lib.ptr(qc), _lib.ptr(Ec), _lib.ptr(tc), _lib.ptr(hc), _lib.ptr(bc), _lib.ptr(rank), B, D, N,
+                                     int(hc.shape[1]) if hc is not None else 0, _lib.ptr(ws), nb, _lib.cur_stream()), "dr4sr_target_rank")
+    return rank
+
+
+@target_rank.register_fake
+def _(q, E, target, hist, item_blocked):
+    return q.new_empty(q.shape[0], dtype=torch.int32)
+
+
+@torch.library.custom_op(f"{NS}::fused_adam_",mutates_args=("params", "adam_m", "adam_v", "state"))
 def fused_adam_(params: torch.Tensor, grads: torch.Tensor, adam_m: torch.Tensor, adam_v: torch.Tensor, state: torch.Tensor,
                 lr: float, beta1: float, beta2: float, eps: float, weight_decay: float) -> None:
     """torch.optim.Adam on flat fp32 buffers; grads has n + 4 floats, grads[n] = the normaliser the gradient is divided by
@@ -228,4 +254,4 @@ def fused_adam_(params: torch.Tensor, grads: torch.Tensor, adam_m: torch.Tensor,
 
 
 OPS = ("embed_gather_posadd", "score_bce", "score_bce_backward", "score_bpr", "score_bpr_backward", "loss_from_scores",
-       "loss_from_scores_backward", "neg_sample", "full_score_topk", "fused_adam_")
+       "loss_from_scores_backward", "neg_sample", "full_score_topk", "target_rank", "fused_adam_")

@@ -328,6 +328,31 @@ int dr4sr_full_score_topk_masked_ws(const float* q, const float* E, const int64_
                                     float* out_score, int64_t* out_item, int64_t B, int32_t D, int32_t n_items, int32_t Lh,
                                     int32_t k, float* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- additive to ABI 10: evaluation by TARGET RANK (csrc/rank.hip).  With one target per row every rank metric at every cutoff is a
+ * function of one integer: rank_out[b] = the number of VALID items that precede target[b] in the order (score descending, id
+ * ascending), counted from 0.  Validity is dr4sr_full_score_topk_masked_ws's, word for word: 1 <= j < n_items, item_blocked[j] == 0
+ * (NULL: nothing blocked), j not among the row's Lh history words (a word counts only if, as an int64, it lies in [0, n_items);
+ * duplicates count once; hist may be NULL with Lh = 0).  A target that is itself not valid (PAD, out of range, blocked, in the row's own
+ * history) gives DR4SR_RANK_NONE.  The scores, the target's included, come from the MFMA loop of the top-k's score GEMM, so for any
+ * finite q / E "rank < k" holds exactly when the top-k call returns the target at position rank.  q [B, D], E [n_items, D], D = 64 or
+ * 128 (else DR4SR_E_SHAPE); B < 0, n_items < 2, Lh < 0 or a null pointer: DR4SR_E_ARG; a null or too small workspace
+ * (dr4sr_target_rank_workspace_bytes): DR4SR_E_WS; B = 0 is a no-op.  Two launches on the caller's stream, no host synchronisation, no
+ * allocation, capturable; integer atomics only: two calls on the same inputs are bitwise equal. */
+#define DR4SR_RANK_NONE 2147483647   /* INT32_MAX */
+int64_t dr4sr_target_rank_workspace_bytes(int64_t B);
+int dr4sr_target_rank(const float* q, const float* E, const int64_t* target, const int64_t* hist, const uint8_t* item_blocked,
+                      int32_t* rank_out, int64_t B, int32_t D, int32_t n_items, int32_t Lh, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+/* One launch of one workgroup ADDS a batch to acc (device, fp64, [1 + 7 * n_cut], zeroed by the caller once per epoch): acc[0] += B, and
+ * per cutoff c (cutoffs: HOST array, n_cut in [1, 8], passed by value) the sums over the rows of ndcg, recall, precision, map, mrr, hit,
+ * f1 in that order — the reference's evaluation/__init__.py formulas for one target per row in IEEE fp64, with h = [rank < c] and
+ * count = [label > 0]: ndcg = label <= eps ? 0 : h / log2(rank + 2); recall = h / count; precision = h / c;
+ * map = h (1 / (rank + 1)) / min(count, c); mrr = h ? 1 / (rank + 1) : 0; hit = h; f1 = 2 h / (count + c).  A row with label <= 0 gives
+ * what those formulas give, NaN included.  The order of the additions is fixed, and calls are ordered by the stream, so an epoch's
+ * accumulator is bitwise reproducible.  Every cutoff must lie in [1, topk] (the reference's map breaks above it): else DR4SR_E_ARG. */
+int dr4sr_rank_metrics_accumulate(const int32_t* rank, const float* label, int64_t B, const int32_t* cutoffs, int32_t n_cut,
+                                  int32_t topk, double* acc, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * FMLP (model/fmlp.py:18-39, module/layers.py:740-807): embedding + position -> LayerNorm -> dropout ->
  * n_layer x { spectral FilterLayer (rfft * complex weight -> irfft, 'ortho') -> dropout -> +x -> LayerNorm ;
