@@ -1831,8 +1831,15 @@ int launch_qkv_embed_bwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int tr
 // output (tiles spread over its 4 waves) for a strided subset of token tiles and adds it to the
 // flat gradient with 128-B-coalesced fp32 atomics at the end.
 
+// (experiments build, DR4SR_WGRAD_NOADD: the launch is timed without its atomic adds — attribution only, the gradients are wrong)
+#ifdef DR4SR_EXPERIMENTS
+#define WGRAD_ADD(P_, V_) do { if (!noadd) unsafeAtomicAdd(P_, V_); } while (0)
+#else
+#define WGRAD_ADD(P_, V_) unsafeAtomicAdd(P_, V_)
+#endif
+
 template <int NG, int KX>
-__device__ __forceinline__ void wgrad_body(const WgradJob& J, const WgradArgs& A, float* __restrict__ part = nullptr) {      // part: wgrad_bf.h
+__device__ __forceinline__ void wgrad_body(const WgradJob& J, const WgradArgs& A, float* __restrict__ part = nullptr, const int noadd = 0) {      // part: wgrad_bf.h
     constexpr int NT = NG / 32, KT = KX / 32, TPW = (NT * KT) / 4;
     static_assert((NT * KT) % 4 == 0, "tile count must split over 4 waves");
     const int T = A.state[DR4SR_STATE_T];
@@ -1924,13 +1931,95 @@ __device__ __forceinline__ void wgrad_body(const WgradJob& J, const WgradArgs& A
         for (int e = 0; e < 16; ++e) {
             const int row = nt * 32 + (e & 3) + 8 * (e >> 2) + 4 * g;
             if (part) part[(size_t)row * KX + kt * 32 + r] = acc[i][e];
-            else unsafeAtomicAdd(J.dW + (size_t)row * (J.ldw ? J.ldw : KX) + kt * 32 + r, acc[i][e]);
+            else WGRAD_ADD(J.dW + (size_t)row * (J.ldw ? J.ldw : KX) + kt * 32 + r, acc[i][e]);
         }
     }
 #pragma unroll
     for (int i = 0; i < (NG + 255) / 256; ++i) {
         const int n = threadIdx.x + 256 * i;
-        if (n < NG && J.db) { if (part) part[(size_t)NG * KX + n] = bsum[i]; else unsafeAtomicAdd(J.db + n, bsum[i]); }
+        if (n < NG && J.db) { if (part) part[(size_t)NG * KX + n] = bsum[i]; else WGRAD_ADD(J.db + n, bsum[i]); }
+    }
+}
+
+// The latency forms' body (k_wgrad_blk<.., TB > 0>): one workgroup owns a [32 TB x 32] block of one weight gradient and a CONTIGUOUS token
+// range — its XCD's share of the batch (xcd_tile's order: the operands are in this XCD's L2) cut into gridDim.x / 8 chunks — and its four
+// waves split the TOKENS: wave w takes the token pairs w, w + 4, ... of the chunk.  Lane (r, g) of a 32x32x2 MFMA feeds G[t = pair + g][n0 + r]
+// and X[t][k0 + r], dword loads that are 128-B-coalesced per half-wave, so the operands go from global memory straight into registers (two
+// batches of U pairs in flight, no LDS, no barrier in the loop).  The four partial tiles are summed through LDS and leave as 1 024 TB atomics.
+// Why: float atomics retire at one 256-B wave-instruction per ~50 ns per CU (MI355X_MICROARCH.md "Global float atomics"); the 64 x 64 block
+// per 64-token tile of wgrad_body<64, 64> is 64 of them per workgroup and ~24 adds per gradient element at the toys B = 256 batch; this
+// form is 16 TB per workgroup and gridDim.x adds per element.  The token range comes from state[T], never from the plan's hint.
+template <int TB>
+__device__ __forceinline__ void wgrad_ksplit_body(const WgradJob& J, const WgradArgs& A, const int noadd = 0) {
+    constexpr int U = 8;
+    const int T = A.state[DR4SR_STATE_T];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, g = lane >> 5;
+    int lo = 0, hi = T, nsub = (int)gridDim.x, sub = (int)blockIdx.x;
+    if (A.xcd > 0 && (gridDim.x & 7) == 0) {
+        const int share = xcd_per((T + A.xcd - 1) / A.xcd, A.xcd) * A.xcd;       // tokens per XCD, a multiple of 64
+        lo = min(T, ((int)blockIdx.x & 7) * share); hi = min(T, lo + share); nsub = (int)gridDim.x >> 3; sub = (int)blockIdx.x >> 3;
+    }
+    const int len = ((hi - lo + nsub - 1) / nsub + 1) & ~1;                      // whole pairs per chunk
+    const int c0 = lo + sub * len, c1 = min(hi, c0 + len);
+    if (c0 >= c1) return;                                                        // no token: nothing to add
+    const int n = (((c1 - c0 + 1) >> 1) + 3 - w) >> 2;                           // this wave's pairs
+    const float* __restrict__ Gp = J.G + J.gcol + r;
+    const float* __restrict__ Xp = J.X + r;
+    f32x16 acc[TB];
+    acc_zero(acc);
+    float bs[TB];
+#pragma unroll
+    for (int b = 0; b < TB; ++b) bs[b] = 0.f;
+    float ga[TB][U], xa[U], gb[TB][U], xb[U];
+    // pairs past the wave's last: the chunk's last token again (the MFMA is skipped); the odd tail's missing token: G = 0
+    auto load = [&](const int i0, float (&gq)[TB][U], float (&xq)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int t = c0 + 2 * (w + 4 * (i0 + u)) + g;
+            const size_t tc = (size_t)min(t, c1 - 1);
+            xq[u] = Xp[tc * J.ldx];
+#pragma unroll
+            for (int b = 0; b < TB; ++b) { const float v = Gp[tc * J.ldg + 32 * b]; gq[b][u] = t < c1 ? v : 0.f; }
+        }
+    };
+    auto mma = [&](const int i0, const float (&gq)[TB][U], const float (&xq)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (i0 + u < n) {
+#pragma unroll
+                for (int b = 0; b < TB; ++b) {
+                    acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(gq[b][u], xq[u], acc[b], 0, 0, 0);
+                    bs[b] += gq[b][u];
+                }
+            }
+        }
+    };
+    if (n > 0) load(0, ga, xa);
+    for (int i0 = 0; i0 < n; i0 += 2 * U) {
+        if (i0 + U < n) load(i0 + U, gb, xb);
+        mma(i0, ga, xa);
+        if (i0 + 2 * U < n) load(i0 + 2 * U, ga, xa);
+        if (i0 + U < n) mma(i0 + U, gb, xb);
+    }
+    float* red = smem;                                                           // [4 waves][32 TB][32]
+#pragma unroll
+    for (int b = 0; b < TB; ++b) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) red[(w * TB + b) * 1024 + ((e & 3) + 8 * (e >> 2) + 4 * g) * 32 + r] = acc[b][e];
+    }
+    lds_barrier();
+#pragma unroll
+    for (int i = 0; i < 4 * TB; ++i) {
+        const int idx = threadIdx.x + 256 * i;
+        const float s = (red[idx] + red[TB * 1024 + idx]) + (red[2 * TB * 1024 + idx] + red[3 * TB * 1024 + idx]);
+        WGRAD_ADD(J.dW + (size_t)(idx >> 5) * J.ldw + (idx & 31), s);
+    }
+    if (J.db) {                                                                  // bias sums: the blocks of column block 0, one 128-B add per wave
+#pragma unroll
+        for (int b = 0; b < TB; ++b) {
+            const float v = bs[b] + __shfl_xor(bs[b], 32);
+            if (g == 0 && n > 0) WGRAD_ADD(J.db + 32 * b + r, v);
+        }
     }
 }
 
@@ -2210,8 +2299,10 @@ __device__ __forceinline__ void owner_job_sorted(const WgradArgs& A, const int o
 // BLK (fp32, batches below the at-scale forms, d = 128): the six whole jobs are cut into 64 x 64 blocks ON THE DEVICE (blockIdx.y ->
 // job, row block, column block): a [128 x 128] job is 128 MFMAs per wave and 16 384 atomics per workgroup on 24 token tiles —
 // four blocks spread that over four workgroups (measured in DESIGN.md section 5.00, round 4).
-template <int D, int F, bool BF, bool SUB = false, bool BLK = false>
-__device__ __forceinline__ void wgrad_kernel_body(const WgradArgs& A, const QkvEmbBwdArgs& Q) {
+// BLK with TB > 0 (what ships, TB = 2): [32 TB x 32] blocks whose four waves split the tokens (wgrad_ksplit_body); blockIdx.x is a token
+// chunk, not a tile.  TB = 0, the 64 x 64 blocks per 64-token tile of round 4, is a kernel of the experiments build (DR4SR_WGRAD_KSPLIT=0)
+template <int D, int F, bool BF, bool SUB = false, bool BLK = false, int TB = 0>
+__device__ __forceinline__ void wgrad_kernel_body(const WgradArgs& A, const QkvEmbBwdArgs& Q, const int noadd = 0) {
     // latency regime (A.qeb_plane): plane z = 0 of the grid is k_qkv_embed_bwd's work (16-row tiles, block-strided), layers shift by one
     const int layer = A.layer0 + (A.qeb_plane ? (int)blockIdx.z - 1 : (int)blockIdx.z);
     if (!SUB && layer < A.layer0) {
@@ -2237,7 +2328,18 @@ __device__ __forceinline__ void wgrad_kernel_body(const WgradArgs& A, const QkvE
         j = (int)blockIdx.y - (A.ow_on ? A.ow_planes : 0) - (A.sc_g ? 1 : 0);
         if (j < 0) { if (tz) scatter_job<D>(A); return; }
     }
-    if constexpr (BLK) {
+    if constexpr (BLK && TB > 0) {
+        constexpr int RB = 32 * TB, NDD = (D / RB) * (D / 32), NFD = (F / RB) * (D / 32), NB = 4 * NDD + NFD + (D / RB) * (F / 32);
+        if (j == NB) { reduce_jobs(A, layer); return; }
+        const int jj = j < 4 * NDD ? j / NDD : (j < 4 * NDD + NFD ? 4 : 5), q = j - (jj < 5 ? jj * NDD : 4 * NDD + NFD);
+        const int ncb = (jj == 5 ? F : D) / 32, rb = q / ncb, cb = q % ncb;      // linear2 is [D x F]: F / 32 column blocks, row stride F
+        WgradJob Jb = A.job[layer * A.jobs_per_layer + jj];
+        const int ldw = Jb.ldw ? Jb.ldw : (jj == 5 ? F : D);
+        Jb.gcol += RB * rb; Jb.X += 32 * cb; Jb.dW += (size_t)RB * rb * ldw + 32 * cb; Jb.ldw = ldw;
+        Jb.db = (Jb.db && cb == 0) ? Jb.db + RB * rb : nullptr;
+        wgrad_ksplit_body<TB>(Jb, A, noadd);
+        return;
+    } else if constexpr (BLK) {
         constexpr int RD = D / 64, RF = F / 64, NDD = RD * RD, NB = 4 * NDD + 2 * RD * RF;
         if (j == NB) { reduce_jobs(A, layer); return; }
         int jj, rb, cb;
@@ -2248,7 +2350,7 @@ __device__ __forceinline__ void wgrad_kernel_body(const WgradArgs& A, const QkvE
         const int ldw = Jb.ldw ? Jb.ldw : (jj == 5 ? F : D);
         Jb.gcol += 64 * rb; Jb.X += 64 * cb; Jb.dW += (size_t)64 * rb * ldw + 64 * cb; Jb.ldw = ldw;
         Jb.db = (Jb.db && cb == 0) ? Jb.db + 64 * rb : nullptr;
-        wgrad_body<64, 64>(Jb, A);
+        wgrad_body<64, 64>(Jb, A, nullptr, noadd);
         return;
     }
     if (j == A.jobs_per_layer) { reduce_jobs(A, layer); return; }
@@ -2274,8 +2376,10 @@ template <int D, int F>
 __global__ __launch_bounds__(256) void k_wgrad_bf(const WgradArgs A, const QkvEmbBwdArgs Q) { wgrad_kernel_body<D, F, true>(A, Q); }
 template <int D, int F>
 __global__ __launch_bounds__(256) void k_wgrad_bf64(const WgradArgs A, const QkvEmbBwdArgs Q) { wgrad_kernel_body<D, F, true, true>(A, Q); }
-template <int D, int F>
-__global__ __launch_bounds__(256) void k_wgrad_blk(const WgradArgs A, const QkvEmbBwdArgs Q) { wgrad_kernel_body<D, F, false, false, true>(A, Q); }
+template <int D, int F, int TB = 0>
+__global__ __launch_bounds__(256) void k_wgrad_blk(const WgradArgs A, const QkvEmbBwdArgs Q, const int noadd) {
+    wgrad_kernel_body<D, F, false, false, true, TB>(A, Q, noadd);
+}
 
 
 // ---- deterministic mode: the partial results k_wgrad's jobs stored (WgradArgs::det*) summed in a FIXED order into the flat gradient.
@@ -2545,8 +2649,18 @@ int launch_wgrad(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, 
     // (three alternating pairs), 0.2284 -> 0.2152 ms at d = 128 (the [128 x 128] jobs were 42 us of it).  DR4SR_WGRAD_BLK=0: whole jobs
     const char* blk_env = DR4SR_XENV("DR4SR_WGRAD_BLK");
     const bool blk64 = !A.bf16x3 && !scatter && (blk_env ? atoi(blk_env) != 0 : !ws.scale);      // (never with table jobs in the launch: k_wgrad_blk has none)
-    const int NY = blk64 ? 4 * (D / 64) * (D / 64) + 2 * (D / 64) * (F / 64) : NJ;
-    if (blk64 && !scatter) lds = sizeof(float) * 64 * 128;
+    // ... with the tokens split over the waves of a workgroup (wgrad_ksplit_body): [64 x 32] blocks, blockIdx.x = the 8 XCD shares of the batch, one
+    // chunk each, whatever the batch holds (the kernel cuts the real T).  Measured, the launch at toys-shaped rows, us (NOTEBOOK "Weight
+    // gradients: tokens split over the waves"): B = 256 12.1 -> 10.1 (d = 128: 26.7 -> 20.6), B = 512 19.7 -> 18.0, B = 768 25.0 -> 18.5,
+    // B = 1 024 37.4 -> 27.5, B = 1 400 40.1 -> 35.4; 16 / 32 splits: 10.4 / - at B = 256, 24.5 / 27.5 at B = 768, 32.1 / 36.2 at B = 1 024.
+    // DR4SR_WGRAD_KSPLIT (experiments build): 0 the 64 x 64 blocks per token tile, 1 / 2 = [32 x 32] / [64 x 32]; DR4SR_WGRAD_GW there: the splits
+    const char* ks_env = DR4SR_XENV("DR4SR_WGRAD_KSPLIT");
+    const int ks = !blk64 ? 0 : ks_env ? atoi(ks_env) : 2;
+    if (ks < 0 || ks > 2) return DR4SR_E_ARG;
+    if (ks) gw = gw_env && gw_max > 0 ? gw_max : 8;
+    const int NY = ks ? (4 * D * D + 2 * D * F) / (1024 * ks) : blk64 ? 4 * (D / 64) * (D / 64) + 2 * (D / 64) * (F / 64) : NJ;
+    if (blk64 && !scatter) lds = sizeof(float) * 64 * 128;          // (the four partial tiles of wgrad_ksplit_body: 4 x 32 TB x 32 floats fit too)
+    const int noadd = DR4SR_XENV("DR4SR_WGRAD_NOADD") ? atoi(DR4SR_XENV("DR4SR_WGRAD_NOADD")) : 0;      // attribution: time the launch without its atomic adds
     if (A.det) {                                            // partial blocks must hold this launch's widest job (checked BEFORE anything is written)
         if (blk64 || gw > DR4SR_DET_MAX_SPLITS) return DR4SR_E_SHAPE;
         for (int jj = 0; jj < NJ; ++jj) {
@@ -2558,7 +2672,13 @@ int launch_wgrad(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, 
     dim3 grid(gw, (gemm ? NY + 1 : 0) + (scatter ? 1 : 0) + A.ow_planes, (gemm ? l_hi - l_lo : 1) + A.qeb_plane), blk(256);
     const size_t lds_q = sizeof(float) * (16 * ((3 * D + 4) + (D + 4)) + (size_t)p->L * D + 16);
     if (A.qeb_plane && lds_q > lds) lds = lds_q;
-#define WG(D_, F_) do { if (blk64) { big_lds(k_wgrad_blk<D_, F_>, lds); hipLaunchKernelGGL((k_wgrad_blk<D_, F_>), grid, blk, lds, s, A, Q); } \
+#define WGB(D_, F_, TB_) do { big_lds((k_wgrad_blk<D_, F_, TB_>), lds); hipLaunchKernelGGL((k_wgrad_blk<D_, F_, TB_>), grid, blk, lds, s, A, Q, noadd); } while (0)
+#ifdef DR4SR_EXPERIMENTS                /* the forms the sweep rejected: kernels of the experiments build only */
+#define WGX(D_, F_) if (blk64 && ks == 0) WGB(D_, F_, 0); else if (ks == 1) WGB(D_, F_, 1); else
+#else
+#define WGX(D_, F_)
+#endif
+#define WG(D_, F_) do { WGX(D_, F_) if (blk64) WGB(D_, F_, 2); \
                         else if (sub64) { big_lds(k_wgrad_bf64<D_, F_>, lds); hipLaunchKernelGGL((k_wgrad_bf64<D_, F_>), grid, blk, lds, s, A, Q); } \
                         else if (A.bf16x3) { big_lds(k_wgrad_bf<D_, F_>, lds); hipLaunchKernelGGL((k_wgrad_bf<D_, F_>), grid, blk, lds, s, A, Q); } \
                         else { big_lds(k_wgrad<D_, F_>, lds); hipLaunchKernelGGL((k_wgrad<D_, F_>), grid, blk, lds, s, A, Q); } } while (0)
@@ -2567,6 +2687,8 @@ int launch_wgrad(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, 
     else if (D == 64 && F == 256) WG(64, 256);
     else return DR4SR_E_SHAPE;
 #undef WG
+#undef WGX
+#undef WGB
     if (A.det) {
         DetDims dm;
         for (int jj = 0; jj < NJ; ++jj) {
