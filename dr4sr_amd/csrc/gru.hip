@@ -45,7 +45,7 @@ struct GruWs {
     // deterministic mode (DR4SR_DETERMINISTIC / train.deterministic; round 6): no fp32 atomics in the step.  The separate glue launches run at every
     // size (their y and d x rows live in global memory); the scorer leaves records de_rec [T] {target, negative, dpos, dneg} instead of its
     // atomics, k_gru_det_rows masks d x in place and writes the rows' ids idx32 [T], the item-table gradient is owner-computed in token order
-    // (linear.hip launch_table_owner64); the 64 x 64 weight-gradient jobs store one block per token split (det_part [job][split][64 x 64 + 64])
+    // (linear.hip launch_table_owner64 / 128); the 64 x 64 weight-gradient jobs store one block per token split (det_part [job][split][64 x 64 + 64])
     // and k_wgrad64_det_reduce adds them in split order
     bool det; float* det_part; int* idx32; int4* de_rec;
     GruLayerWs layer[GRU_MAX_LAYERS];
@@ -75,7 +75,7 @@ static bool gru_det() { const char* e = DR4SR_ENV("DR4SR_DETERMINISTIC"); return
 static int gru_check(const dr4sr_gru4rec_plan* p) {
     if (!p || p->abi_version != DR4SR_ABI_VERSION) return DR4SR_E_ARG;
     if (p->B <= 0 || p->L <= 0 || p->n_items < 2 || p->n_layer <= 0 || p->n_layer > GRU_MAX_LAYERS) return DR4SR_E_ARG;
-    if (p->D != 64 || (p->H != 128 && p->H != 256) || p->L > 64) return DR4SR_E_SHAPE;
+    if ((p->D != 64 && p->D != 128) || (p->H != 128 && p->H != 256) || p->L > 64) return DR4SR_E_SHAPE;
     if (!(p->p_drop >= 0.f && p->p_drop < 1.f) || !p->params || !p->state || !p->in_item_id || !p->seqlen) return DR4SR_E_ARG;
     return 0;
 }
@@ -124,7 +124,7 @@ static void gru_carve(const dr4sr_gru4rec_plan* p, GruWs* ws) {
 
 extern "C" int64_t dr4sr_gru4rec_workspace_bytes(const dr4sr_gru4rec_plan* plan) {
     if (!plan || plan->B <= 0 || plan->L <= 0 || plan->n_layer <= 0 || plan->n_layer > GRU_MAX_LAYERS) return DR4SR_E_ARG;
-    if (plan->D != 64 || (plan->H != 128 && plan->H != 256) || plan->L > 64) return DR4SR_E_SHAPE;       // as gru_check
+    if ((plan->D != 64 && plan->D != 128) || (plan->H != 128 && plan->H != 256) || plan->L > 64) return DR4SR_E_SHAPE;       // as gru_check
     dr4sr_gru4rec_plan q = *plan;
     q.workspace = nullptr;
     GruWs ws;
@@ -284,9 +284,13 @@ struct GruGlueArgs {
     const float* in; float* out0; float* out1; float* out2;   // kernel-specific tensors, see each kernel
 };
 
-// out0 = X0 [T,64] (written by the blockIdx.y == 0 workgroups), out1 = gi_1 [T, 3H]; W = W_ih1 [3H][64].  grid (tiles, 3H / 64)
+// All three are templates on the embedding width D (64 or 128): a thread of the row passes of k_gru_embed_gi and k_gru_mid owns the float4 at
+// columns 4 (tid % 16) + 64 u, u < D / 64, of row tid / 16, k_gru_dx_embed splits the columns over
+// blockIdx.y; the dropout element index is ((b L + pos) D + column), k_embed_fwd<D>'s.
+// out0 = X0 [T,D] (written by the blockIdx.y == 0 workgroups), out1 = gi_1 [T, 3H]; W = W_ih1 [3H][D].  grid (tiles, 3H / 64)
+template <int D>
 __global__ __launch_bounds__(256) void k_gru_embed_gi(const GruGlueArgs A, const int N3) {
-    constexpr int D = 64, LDA = D + 4;
+    constexpr int LDA = D + 4, VPL = D / 64;
     const int T = A.state[DR4SR_STATE_T], t0 = blockIdx.x * 16;
     if (t0 >= T) return;
     const int n0 = blockIdx.y * 64;
@@ -294,22 +298,32 @@ __global__ __launch_bounds__(256) void k_gru_embed_gi(const GruGlueArgs A, const
     WFragT<D, 64> f;
     wfrag_load(f, A.W + (size_t)n0 * D, D);
     {
-        const int r = threadIdx.x >> 4, c = (threadIdx.x & 15) * 4, t = t0 + r;
-        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        const int r = threadIdx.x >> 4, c0 = (threadIdx.x & 15) * 4, t = t0 + r;
+        float4 o[VPL];
+#pragma unroll
+        for (int u = 0; u < VPL; ++u) o[u] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (t < T) {
             const int b = find_seq_from(A.cu, A.B, t, A.tile_seq[t0 >> 4]), pos = t - A.cu[b];
             const int64_t row = A.rows ? A.rows[b] : b;
             int64_t id = A.idx[row * A.L + pos];
             id = id < 0 ? 0 : (id >= A.n_items ? A.n_items - 1 : id);
-            o = ld4(A.E + id * D + c);
+#pragma unroll
+            for (int u = 0; u < VPL; ++u) o[u] = ld4(A.E + id * D + c0 + 64 * u);
             if (A.training && A.p > 0.f) {
                 const RngKey rk = make_rng(A.seed, (uint32_t)A.state[DR4SR_STATE_RNGSTEP], A.p);
-                const float4 m = drop4(rk, DR4SR_SITE_EMB, ((uint64_t)b * A.L + pos) * D + c);
-                o.x *= m.x; o.y *= m.y; o.z *= m.z; o.w *= m.w;
+#pragma unroll
+                for (int u = 0; u < VPL; ++u) {
+                    const float4 m = drop4(rk, DR4SR_SITE_EMB, ((uint64_t)b * A.L + pos) * D + c0 + 64 * u);
+                    o[u].x *= m.x; o[u].y *= m.y; o[u].z *= m.z; o[u].w *= m.w;
+                }
             }
-            if (blockIdx.y == 0) st4(A.out0 + (size_t)t * D + c, o);
+            if (blockIdx.y == 0) {
+#pragma unroll
+                for (int u = 0; u < VPL; ++u) st4(A.out0 + (size_t)t * D + c0 + 64 * u, o[u]);
+            }
         }
-        st4(As + r * LDA + c, o);
+#pragma unroll
+        for (int u = 0; u < VPL; ++u) st4(As + r * LDA + c0 + 64 * u, o[u]);
     }
     lds_barrier();
     TileAcc<16, 64> acc;
@@ -318,34 +332,38 @@ __global__ __launch_bounds__(256) void k_gru_embed_gi(const GruGlueArgs A, const
     tile_to_global<16, 64>(acc, A.out1 + n0, N3, nullptr, t0, T);
 }
 
-// in = h_top [T,H]; out0 = d y [T,64] (kept for the weight gradient), out1 = d h_top [T,H]; W = W_out [64][H], bias = b_out.  grid (tiles)
-template <int H>
+// in = h_top [T,H]; out0 = d y [T,D] (kept for the weight gradient), out1 = d h_top [T,H]; W = W_out [D][H], bias = b_out.  grid (tiles)
+// Registers at D = 128: the W_out^T fragments (H D / 256 floats per lane) die with the y product before the W_out fragments of d h (as many)
+// are requested, so the two never live together (no scratch in any instantiation).
+template <int H, int D>
 __global__ __launch_bounds__(256) void k_gru_mid(const GruGlueArgs A) {
-    constexpr int D = 64, LDA = H + 4, LDY = D + 4;
+    constexpr int LDA = H + 4, LDY = D + 4, VPL = D / 64;
     const int T = A.state[DR4SR_STATE_T], t0 = blockIdx.x * 16, tile = blockIdx.x;
     if (t0 >= T) return;
     float* As = smem;                                   // [16][LDA]  h tile
     float* Ys = As + 16 * LDA;                          // [16][LDY]  y tile, then d y tile
     float* red = Ys + 16 * LDY;                         // [8]
-    WFragT<H, 64> fy;
-    wfrag_load(fy, A.W, H);
-    load_tile_bm<16, H>(As, LDA, A.in, H, t0, T);
-    lds_barrier();
     {
-        TileAcc<16, 64> acc;
+        WFragT<H, D> fy;
+        wfrag_load(fy, A.W, H);
+        load_tile_bm<16, H>(As, LDA, A.in, H, t0, T);
+        lds_barrier();
+        TileAcc<16, D> acc;
         tile_zero(acc);
-        tile_mma_frag<16, H, 64>(As, LDA, fy, acc);
-        tile_to_lds<16, 64>(acc, Ys, LDY, A.bias);
+        tile_mma_frag<16, H, D>(As, LDA, fy, acc);
+        tile_to_lds<16, D>(acc, Ys, LDY, A.bias);
     }
     WFragC<D, H> fd;                                    // d h = d y W_out: requested now, the round trip overlaps the scorer
     wfrag_load(fd, A.W, H);
     lds_barrier();
     // ---- scorer: 16 lanes per row (model/basemodel.py:204-214, model/loss_func.py:9-38; same draws / terms as k_score_packed)
     {
-        const int r = threadIdx.x >> 4, sub = threadIdx.x & 15, c = sub * 4, t = t0 + r;
+        const int r = threadIdx.x >> 4, sub = threadIdx.x & 15, c0 = sub * 4, t = t0 + r;
         const RngKey rk = make_rng(A.seed, (uint32_t)A.state[DR4SR_STATE_RNGSTEP], 0.f);
         float lsum = 0.f, cnt = 0.f;
-        float4 dz = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 dz[VPL];
+#pragma unroll
+        for (int u = 0; u < VPL; ++u) dz[u] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (t < T) {
             const int b = find_seq_from(A.cu, A.B, t, A.tile_seq[t0 >> 4]), pos = t - A.cu[b], n = A.cu[b + 1] - A.cu[b];
             const int64_t row = A.rows ? A.rows[b] : b;
@@ -359,18 +377,36 @@ __global__ __launch_bounds__(256) void k_gru_mid(const GruGlueArgs A) {
             }
             ng = ng < 0 ? 0 : (ng >= A.n_items ? A.n_items - 1 : ng);
             if (tgt > 0 && tgt < A.n_items) {
-                const float4 q = ld4(Ys + r * LDY + c), ep = ld4(A.E + tgt * D + c), en = ld4(A.E + ng * D + c);
-                const float sp = group16_sum(q.x * ep.x + q.y * ep.y + q.z * ep.z + q.w * ep.w);
-                const float sn = group16_sum(q.x * en.x + q.y * en.y + q.z * en.z + q.w * en.w);
+                float4 q[VPL], ep[VPL], en[VPL];
+#pragma unroll
+                for (int u = 0; u < VPL; ++u) {
+                    const int c = c0 + 64 * u;
+                    q[u] = ld4(Ys + r * LDY + c); ep[u] = ld4(A.E + tgt * D + c); en[u] = ld4(A.E + ng * D + c);
+                }
+                float pp = q[0].x * ep[0].x + q[0].y * ep[0].y + q[0].z * ep[0].z + q[0].w * ep[0].w;
+                float pn = q[0].x * en[0].x + q[0].y * en[0].y + q[0].z * en[0].z + q[0].w * en[0].w;
+#pragma unroll
+                for (int u = 1; u < VPL; ++u) {
+                    pp += q[u].x * ep[u].x + q[u].y * ep[u].y + q[u].z * ep[u].z + q[u].w * ep[u].w;
+                    pn += q[u].x * en[u].x + q[u].y * en[u].y + q[u].z * en[u].z + q[u].w * en[u].w;
+                }
+                const float sp = group16_sum(pp);
+                const float sn = group16_sum(pn);
                 const float dpos = -sigmoid_f(-sp), dneg = sigmoid_f(sn);
                 if (sub == 0) { lsum += softplus_f(-sp) + softplus_f(sn); cnt += 1.f; }
-                dz = make_float4(dpos * ep.x + dneg * en.x, dpos * ep.y + dneg * en.y, dpos * ep.z + dneg * en.z, dpos * ep.w + dneg * en.w);
-                float* gp = A.dE + tgt * D + c;
-                float* gn = A.dE + ng * D + c;
-                unsafeAtomicAdd(gp, dpos * q.x); unsafeAtomicAdd(gp + 1, dpos * q.y); unsafeAtomicAdd(gp + 2, dpos * q.z); unsafeAtomicAdd(gp + 3, dpos * q.w);
-                unsafeAtomicAdd(gn, dneg * q.x); unsafeAtomicAdd(gn + 1, dneg * q.y); unsafeAtomicAdd(gn + 2, dneg * q.z); unsafeAtomicAdd(gn + 3, dneg * q.w);
+#pragma unroll
+                for (int u = 0; u < VPL; ++u) {
+                    const int c = c0 + 64 * u;
+                    dz[u] = make_float4(dpos * ep[u].x + dneg * en[u].x, dpos * ep[u].y + dneg * en[u].y, dpos * ep[u].z + dneg * en[u].z,
+                                        dpos * ep[u].w + dneg * en[u].w);
+                    float* gp = A.dE + tgt * D + c;
+                    float* gn = A.dE + ng * D + c;
+                    unsafeAtomicAdd(gp, dpos * q[u].x); unsafeAtomicAdd(gp + 1, dpos * q[u].y); unsafeAtomicAdd(gp + 2, dpos * q[u].z); unsafeAtomicAdd(gp + 3, dpos * q[u].w);
+                    unsafeAtomicAdd(gn, dneg * q[u].x); unsafeAtomicAdd(gn + 1, dneg * q[u].y); unsafeAtomicAdd(gn + 2, dneg * q[u].z); unsafeAtomicAdd(gn + 3, dneg * q[u].w);
+                }
             }
-            st4(A.out0 + (size_t)t * D + c, dz);
+#pragma unroll
+            for (int u = 0; u < VPL; ++u) st4(A.out0 + (size_t)t * D + c0 + 64 * u, dz[u]);
             if (pos == n - 1) {                           // positions behind the sequence (zero query): loss terms only, negatives drawn as the unfused scorer draws them
                 for (int l = n + sub; l < A.L; l += 16) {
                     const int64_t tl = A.target[row * A.L + l];
@@ -379,7 +415,8 @@ __global__ __launch_bounds__(256) void k_gru_mid(const GruGlueArgs A) {
                 }
             }
         }
-        st4(Ys + r * LDY + c, dz);                       // (the lanes of a row have all read their q by now: group16_sum)
+#pragma unroll
+        for (int u = 0; u < VPL; ++u) st4(Ys + r * LDY + c0 + 64 * u, dz[u]);   // (the lanes of a row have all read their q by now: group16_sum)
         cnt = wave_sum(cnt); lsum = wave_sum(lsum);
         if ((threadIdx.x & 63) == 0) { red[2 * (threadIdx.x >> 6)] = cnt; red[2 * (threadIdx.x >> 6) + 1] = lsum; }
     }
@@ -394,11 +431,13 @@ __global__ __launch_bounds__(256) void k_gru_mid(const GruGlueArgs A) {
     tile_to_global<16, H>(acc2, A.out1, H, nullptr, t0, T);
 }
 
-// in = d gi_1 [T, 3H]; W = W_ih1 [3H][64]; scatter into dE.  grid (tiles)
-template <int K>
+// in = d gi_1 [T, 3H]; W = W_ih1 [3H][D]; scatter into dE.  grid (tiles, D / 64): a workgroup owns one 64-column block of d x, so that the D = 128
+// launch is twice the D = 64 workgroups with the D = 64 work each.  (One workgroup per tile for all 128 columns streams the whole 393 KB of
+// W_ih1 through 83 workgroups at B = 256: measured 42.7 us, against 36.4 us for the two launches it replaces)
+template <int K, int D>
 __global__ __launch_bounds__(256) void k_gru_dx_embed(const GruGlueArgs A) {
-    constexpr int D = 64, LDA = K + 4;
-    const int T = A.state[DR4SR_STATE_T], t0 = blockIdx.x * 16;
+    constexpr int LDA = K + 4;
+    const int T = A.state[DR4SR_STATE_T], t0 = blockIdx.x * 16, n0 = blockIdx.y * 64;
     if (t0 >= T) return;
     float* As = smem;                                   // [16][LDA]
     float* red = As + 16 * LDA;                         // [16][68] the product's tile
@@ -407,7 +446,7 @@ __global__ __launch_bounds__(256) void k_gru_dx_embed(const GruGlueArgs A) {
     {                                                   // (the split-K form measured slower HERE — 19.0 against 15.1 us: 83 workgroups, one per
         TileAcc<16, 64> acc;                            //  tile, each streaming the whole 196 KB of W_ih1 either way — and faster for the
         tile_zero(acc);                                 //  N = 256 product between the BPTT launches: 20.7 -> 18.6 us)
-        tile_mma_xw<16, K, 64>(As, LDA, A.W, D, acc);
+        tile_mma_xw<16, K, 64>(As, LDA, A.W + n0, D, acc);
         tile_to_lds<16, 64>(acc, red, 68, nullptr);
     }
     lds_barrier();
@@ -420,16 +459,16 @@ __global__ __launch_bounds__(256) void k_gru_dx_embed(const GruGlueArgs A) {
     if (id <= 0 || id >= A.n_items) return;             // padding_idx / out of range: no gradient row
     if (A.training && A.p > 0.f) {
         const RngKey rk = make_rng(A.seed, (uint32_t)A.state[DR4SR_STATE_RNGSTEP], A.p);
-        const float4 m = drop4(rk, DR4SR_SITE_EMB, ((uint64_t)b * A.L + pos) * D + c);
+        const float4 m = drop4(rk, DR4SR_SITE_EMB, ((uint64_t)b * A.L + pos) * D + n0 + c);
         g.x *= m.x; g.y *= m.y; g.z *= m.z; g.w *= m.w;
     }
-    float* d = A.dE + id * D + c;
+    float* d = A.dE + id * D + n0 + c;
     unsafeAtomicAdd(d, g.x); unsafeAtomicAdd(d + 1, g.y); unsafeAtomicAdd(d + 2, g.z); unsafeAtomicAdd(d + 3, g.w);
 }
 
-// the fused glue applies to what the 16-row latency GEMMs apply to (small batches), D = 64
+// the fused glue applies to what the 16-row latency GEMMs apply to (small batches), D = 64 or 128
 static bool gru_glue_fused(const dr4sr_gru4rec_plan* p, int Tmax) {
-    return !DR4SR_ENV("DR4SR_GRU_NOFUSE_GLUE") && !DR4SR_XENV("DR4SR_GRU_GEMM64") && !at_scale(Tmax) && p->D == 64 && (p->H == 128 || p->H == 256)
+    return !DR4SR_ENV("DR4SR_GRU_NOFUSE_GLUE") && !DR4SR_XENV("DR4SR_GRU_GEMM64") && !at_scale(Tmax) && (p->D == 64 || p->D == 128) && (p->H == 128 || p->H == 256)
         && !gru_det();                                      // deterministic mode: the separate launches (the owners read y and d x from global memory)
 }
 
@@ -438,10 +477,11 @@ static int launch_gemm(const float* A, int lda, const float* W, int ldw, const f
     const size_t lds = sizeof(float) * 64 * 68;
     dim3 blk(256);
     const bool no16 = DR4SR_XENV("DR4SR_GRU_GEMM64") != nullptr;          // cross-check switch: 64-row tiles everywhere
-    if (!no16 && !at_scale(Tmax) && N % 64 == 0 && ((colmode && !bias && K == 64) || (!colmode && (K == 64 || K == 128 || K == 256)))) {
+    if (!no16 && !at_scale(Tmax) && N % 64 == 0 && ((colmode && !bias && (K == 64 || K == 128)) || (!colmode && (K == 64 || K == 128 || K == 256)))) {
         const size_t l16 = sizeof(float) * 16 * (K + 4);
         dim3 grid((Tmax + 15) / 16, N / 64);
-        if (colmode) hipLaunchKernelGGL(k_gemm16_col<64>, grid, blk, l16, s, A, lda, W, ldw, C, ldc, state);
+        if (colmode && K == 64) hipLaunchKernelGGL(k_gemm16_col<64>, grid, blk, l16, s, A, lda, W, ldw, C, ldc, state);
+        else if (colmode) hipLaunchKernelGGL(k_gemm16_col<128>, grid, blk, l16, s, A, lda, W, ldw, C, ldc, state);      // d h = d y W_out at D = 128
         else if (K == 64) hipLaunchKernelGGL(k_gemm16_row<64>, grid, blk, l16, s, A, lda, W, ldw, bias, C, ldc, state);
         else if (K == 128) hipLaunchKernelGGL(k_gemm16_row<128>, grid, blk, l16, s, A, lda, W, ldw, bias, C, ldc, state);
         else hipLaunchKernelGGL(k_gemm16_row<256>, grid, blk, l16, s, A, lda, W, ldw, bias, C, ldc, state);
@@ -531,21 +571,25 @@ __global__ __launch_bounds__(256) void k_wgrad64_det_reduce(const Wg64Args A, co
     else M.db[n0 + e - 64 * 64] += sum;
 }
 // deterministic mode: g = d x[t] * the embedding dropout mask, in place, + the row's id (0: no gradient row) for the owners
+template <int D>
 __global__ __launch_bounds__(256) void k_gru_det_rows(float* __restrict__ dX, int* __restrict__ idx32, const int64_t* __restrict__ idx,
                                                       const int64_t* __restrict__ rows, const int* __restrict__ cu, int B, int L, int n_items,
                                                       const int* __restrict__ state, uint64_t seed, float p, int training) {
-    constexpr int D = 64;
-    const int T = state[DR4SR_STATE_T], t = blockIdx.x * 16 + (threadIdx.x >> 4), c = (threadIdx.x & 15) * 4;
+    const int T = state[DR4SR_STATE_T], t = blockIdx.x * 16 + (threadIdx.x >> 4), c0 = (threadIdx.x & 15) * 4;
     if (t >= T) return;
     const int b = find_seq(cu, B, t), pos = t - cu[b];
     const int64_t row = rows ? rows[b] : b;
     const int64_t id = idx[row * L + pos];
     if (training && p > 0.f) {
         const RngKey rk = make_rng(seed, (uint32_t)state[DR4SR_STATE_RNGSTEP], p);
-        const float4 m = drop4(rk, DR4SR_SITE_EMB, ((uint64_t)b * L + pos) * D + c);
-        float4 g = ld4(dX + (size_t)t * D + c);
-        g.x *= m.x; g.y *= m.y; g.z *= m.z; g.w *= m.w;
-        st4(dX + (size_t)t * D + c, g);
+#pragma unroll
+        for (int u = 0; u < D / 64; ++u) {
+            const int c = c0 + 64 * u;
+            const float4 m = drop4(rk, DR4SR_SITE_EMB, ((uint64_t)b * L + pos) * D + c);
+            float4 g = ld4(dX + (size_t)t * D + c);
+            g.x *= m.x; g.y *= m.y; g.z *= m.z; g.w *= m.w;
+            st4(dX + (size_t)t * D + c, g);
+        }
     }
     if ((threadIdx.x & 15) == 0) idx32[t] = (id > 0 && id < n_items) ? (int)id : 0;
 }
@@ -841,7 +885,9 @@ static int gru_embed_gi(const dr4sr_gru4rec_plan* p, const GruWs& ws, int traini
     if (gru_glue_fused(p, ws.Tmax)) {
         GruGlueArgs A = glue_args(p, ws, training);
         A.W = p->params + ws.off_wih[0]; A.out0 = ws.X0; A.out1 = ws.layer[0].gi;
-        hipLaunchKernelGGL(k_gru_embed_gi, dim3((ws.Tmax + 15) / 16, 3 * H / 64), dim3(256), sizeof(float) * 16 * (D + 4), s, A, 3 * H);
+        const dim3 grid((ws.Tmax + 15) / 16, 3 * H / 64);
+        if (D == 64) hipLaunchKernelGGL(k_gru_embed_gi<64>, grid, dim3(256), sizeof(float) * 16 * (D + 4), s, A, 3 * H);
+        else hipLaunchKernelGGL(k_gru_embed_gi<128>, grid, dim3(256), sizeof(float) * 16 * (D + 4), s, A, 3 * H);
         return DR4SR_LAUNCH_CHECK();
     }
     RC(launch_embed_fwd_raw(p->params + ws.off_E, nullptr, p->in_item_id, p->rows, ws.cu, ws.X0, p->B, p->L, D, p->n_items, p->state,
@@ -899,13 +945,18 @@ static int gru_forward(const dr4sr_gru4rec_plan* p, const GruWs& ws, int trainin
 // output projection + scorer / BCE + d h_top in one launch (training step, latency regime); returns -100 when it does not apply
 static int gru_mid(const dr4sr_gru4rec_plan* p, const GruWs& ws, hipStream_t s) {
     if (!gru_glue_fused(p, ws.Tmax)) return -100;
-    const int H = p->H;
+    const int D = p->D, H = p->H;
     GruGlueArgs A = glue_args(p, ws, 1);
     A.W = p->params + ws.off_ow; A.bias = p->params + ws.off_ob; A.in = ws.layer[p->n_layer - 1].hout; A.out0 = ws.dY; A.out1 = ws.dH;
-    const size_t lds = sizeof(float) * (16 * (H + 4) + 16 * 68 + 8);
+    const size_t lds = sizeof(float) * (16 * (H + 4) + 16 * (D + 4) + 8);
     dim3 grid((ws.Tmax + 15) / 16);
-    if (H == 256) hipLaunchKernelGGL(k_gru_mid<256>, grid, dim3(256), lds, s, A);
-    else hipLaunchKernelGGL(k_gru_mid<128>, grid, dim3(256), lds, s, A);
+    if (D == 64) {
+        if (H == 256) hipLaunchKernelGGL((k_gru_mid<256, 64>), grid, dim3(256), lds, s, A);
+        else hipLaunchKernelGGL((k_gru_mid<128, 64>), grid, dim3(256), lds, s, A);
+    } else {
+        if (H == 256) hipLaunchKernelGGL((k_gru_mid<256, 128>), grid, dim3(256), lds, s, A);
+        else hipLaunchKernelGGL((k_gru_mid<128, 128>), grid, dim3(256), lds, s, A);
+    }
     return DR4SR_LAUNCH_CHECK();
 }
 
@@ -915,22 +966,25 @@ static int gru_dx_embed(const dr4sr_gru4rec_plan* p, const GruWs& ws, int traini
     if (gru_glue_fused(p, ws.Tmax)) {
         GruGlueArgs A = glue_args(p, ws, training);
         A.W = p->params + ws.off_wih[0]; A.in = ws.layer[0].dgi;
-        dim3 grid((ws.Tmax + 15) / 16);
-        if (H == 256) {
-            const size_t lds = sizeof(float) * (16 * (768 + 4) + 16 * 68);
-            big_lds(k_gru_dx_embed<768>, lds);
-            hipLaunchKernelGGL(k_gru_dx_embed<768>, grid, dim3(256), lds, s, A);
+        dim3 grid((ws.Tmax + 15) / 16, D / 64);
+        const size_t lds = sizeof(float) * (16 * (3 * H + 4) + 16 * 68);          // K = 768: 53 760 bytes, above the 48 KB default (big_lds)
+        if (D == 64) {
+            if (H == 256) { big_lds(k_gru_dx_embed<768, 64>, lds); hipLaunchKernelGGL((k_gru_dx_embed<768, 64>), grid, dim3(256), lds, s, A); }
+            else hipLaunchKernelGGL((k_gru_dx_embed<384, 64>), grid, dim3(256), lds, s, A);
         } else {
-            const size_t lds = sizeof(float) * (16 * (384 + 4) + 16 * 68);
-            hipLaunchKernelGGL(k_gru_dx_embed<384>, grid, dim3(256), lds, s, A);
+            if (H == 256) { big_lds(k_gru_dx_embed<768, 128>, lds); hipLaunchKernelGGL((k_gru_dx_embed<768, 128>), grid, dim3(256), lds, s, A); }
+            else hipLaunchKernelGGL((k_gru_dx_embed<384, 128>), grid, dim3(256), lds, s, A);
         }
         return DR4SR_LAUNCH_CHECK();
     }
     RC(launch_gemm(ws.layer[0].dgi, 3 * H, p->params + ws.off_wih[0], D, nullptr, ws.dX0, D, 3 * H, D, true, ws.Tmax, p->state, s));
     if (ws.det) {                                           // d E: the scorer's records (fused step only) + the masked d x rows, owner-computed in token order
-        hipLaunchKernelGGL(k_gru_det_rows, dim3((ws.Tmax + 15) / 16), dim3(256), 0, s, ws.dX0, ws.idx32, p->in_item_id, p->rows, ws.cu, p->B, p->L,
-                           p->n_items, p->state, p->seed, p->p_drop, training);
-        return launch_table_owner64(p->state, with_score ? ws.de_rec : nullptr, ws.idx32, ws.Y, ws.dX0, p->grads + ws.off_E, p->n_items, s);
+        if (D == 64) hipLaunchKernelGGL(k_gru_det_rows<64>, dim3((ws.Tmax + 15) / 16), dim3(256), 0, s, ws.dX0, ws.idx32, p->in_item_id, p->rows, ws.cu, p->B, p->L,
+                                        p->n_items, p->state, p->seed, p->p_drop, training);
+        else hipLaunchKernelGGL(k_gru_det_rows<128>, dim3((ws.Tmax + 15) / 16), dim3(256), 0, s, ws.dX0, ws.idx32, p->in_item_id, p->rows, ws.cu, p->B, p->L,
+                                p->n_items, p->state, p->seed, p->p_drop, training);
+        if (D == 64) return launch_table_owner64(p->state, with_score ? ws.de_rec : nullptr, ws.idx32, ws.Y, ws.dX0, p->grads + ws.off_E, p->n_items, s);
+        return launch_table_owner128(p->state, with_score ? ws.de_rec : nullptr, ws.idx32, ws.Y, ws.dX0, p->grads + ws.off_E, p->n_items, s);
     }
     return launch_embed_bwd_raw(ws.dX0, p->in_item_id, p->rows, ws.cu, p->grads + ws.off_E, nullptr, p->B, p->L, D, p->n_items, p->state,
                                 p->seed, p->p_drop, training, s);

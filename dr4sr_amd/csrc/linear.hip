@@ -2493,17 +2493,26 @@ __global__ __launch_bounds__(256) void k_fmlp_wgrad_bf64(const WgradArgs A) {
 }
 // the owner-computed item-table gradient (owner_job above) as a launch of its own: FMLP's deterministic mode.  rec == NULL: no scorer stream
 __global__ __launch_bounds__(256) void k_table_owner64(const WgradArgs A) { owner_job<64>(A, blockIdx.x); }
-int launch_table_owner64(const int* state, const int4* rec, const int* idx32, const float* z, const float* g, float* dE, int n_items, hipStream_t s) {
+__global__ __launch_bounds__(256) void k_table_owner128(const WgradArgs A) { owner_job<128>(A, blockIdx.x); }     // GRU4Rec's, embed_dim 128
+template <int D, typename KERNEL>
+static int launch_table_owner(KERNEL kernel, const int* state, const int4* rec, const int* idx32, const float* z, const float* g, float* dE, int n_items,
+                              hipStream_t s) {
     WgradArgs A{};
     int logG = 8;
-    auto lds_of = [&](int lg) { return sizeof(float) * 4 * (size_t)((n_items + (1 << lg) - 1) >> lg) * 64 + 4 * 16 * 4 * sizeof(int); };
+    auto lds_of = [&](int lg) { return sizeof(float) * 4 * (size_t)((n_items + (1 << lg) - 1) >> lg) * D + 4 * 16 * 4 * sizeof(int); };
     while (lds_of(logG) > 96 * 1024 && logG < 20) ++logG;
     A.state = state; A.ow_on = 1; A.ow_rec = rec; A.ow_idx32 = idx32; A.ow_z = z; A.sc_g = g; A.sc_dE = dE; A.sc_n_items = n_items;
     A.ow_logG = logG; A.ow_rpo = (n_items + (1 << logG) - 1) >> logG;
     const size_t lds = lds_of(logG);
-    big_lds(k_table_owner64, lds);
-    hipLaunchKernelGGL(k_table_owner64, dim3(1 << logG), dim3(256), lds, s, A);
+    big_lds(kernel, lds);
+    hipLaunchKernelGGL(kernel, dim3(1 << logG), dim3(256), lds, s, A);
     return DR4SR_LAUNCH_CHECK();
+}
+int launch_table_owner64(const int* state, const int4* rec, const int* idx32, const float* z, const float* g, float* dE, int n_items, hipStream_t s) {
+    return launch_table_owner<64>(k_table_owner64, state, rec, idx32, z, g, dE, n_items, s);
+}
+int launch_table_owner128(const int* state, const int4* rec, const int* idx32, const float* z, const float* g, float* dE, int n_items, hipStream_t s) {
+    return launch_table_owner<128>(k_table_owner128, state, rec, idx32, z, g, dE, n_items, s);
 }
 int launch_fmlp_wgrad(const WgradArgs& A, int Tmax, int n_layer, hipStream_t s) {
     const int ntiles = (Tmax + 63) / 64;

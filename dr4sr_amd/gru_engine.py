@@ -23,7 +23,7 @@ def gru_param_shapes(n_items, D, H, n_layer):
 
 class GruEngine(FlatEngine):
     MODEL, PLAN, PREFIX, ADAM_STEP = "GRU4Rec", _lib.GruPlan, "dr4sr_gru4rec_", "dr4sr_gru4rec_adam_step"
-    BUILT_FOR = "L <= 64, D = 64, hidden 128 or 256"
+    BUILT_FOR = "L <= 64, D = 64 or 128, hidden 128 or 256"
     POOLED = (_lib.POOL_LAST,)
     train_steps = FlatEngine._train_steps
 

@@ -409,7 +409,7 @@ int dr4sr_optimizer_flat(int32_t optimizer, float* params, const float* grads, f
 
 /* ------------------------------------------------------------------------------------------------
  * GRU4Rec (model/gru4rec.py:12-34; module/layers.py:117-136 = torch.nn.GRU(bias=False, batch_first, n_layer) + Linear(H->D)):
- * x = dropout(E[idx]) -> GRU -> Linear -> 'origin'/'last' pooling -> scorer + BCE as SASRec.  D = 64, H in {128, 256},
+ * x = dropout(E[idx]) -> GRU -> Linear -> 'origin'/'last' pooling -> scorer + BCE as SASRec.  D in {64, 128}, H in {128, 256},
  * n_layer <= 4, L <= 64.  Only rows < seqlen are computed (post-padded rows; the recurrence is causal).
  * Flat parameter layout: E[N,D] | per layer: weight_ih_l[3H,in] weight_hh_l[3H,H] | out_w[D,H] out_b[D]
  *   (names: item_embedding.weight == query_encoder.0.1.weight, query_encoder.0.3.gru.weight_{ih,hh}_l{l},
@@ -448,7 +448,7 @@ int64_t dr4sr_gru4rec_param_layout(int32_t n_items, int32_t D, int32_t H, int32_
  * a wait that runs out never hangs the GPU but sets a sticky error flag — the int32 word 2 of the workspace (words 0, 1: launch
  * counter, finish ticket) — and leaves garbage; the caller should read that word whenever it synchronises anyway (per epoch) and
  * treat non-zero as a failed run. */
-/* bytes, or DR4SR_E_SHAPE unless D = 64, H in {128, 256}, L <= 64 */
+/* bytes, or DR4SR_E_SHAPE unless D in {64, 128}, H in {128, 256}, L <= 64 */
 int64_t dr4sr_gru4rec_workspace_bytes(const dr4sr_gru4rec_plan* plan);
 /* the optimizer half of dr4sr_gru4rec_train_step on the plan's buffers (plan->optimizer, loss_log): data parallel = fwd_bwd,
  * all-reduce of plan->grads, this */

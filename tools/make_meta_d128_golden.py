@@ -25,9 +25,10 @@ PART_LIMIT = 900 * 1024                                               # compress
 BIG = ("param.", "inner.grad.", "outer.grad_val.")                    # what goes to the parts
 
 
-def split(arrays, out_dir):
-    small = {k: v for k, v in arrays.items() if not k.startswith(BIG)}
-    big = [k for k in arrays if k.startswith(BIG)]
+def split(arrays, out_dir, name=NAME, big_prefixes=BIG):
+    """<name>.npz with the small arrays and meta.n_parts + <name>.part<i>.npz with the arrays whose key starts with one of big_prefixes"""
+    small = {k: v for k, v in arrays.items() if not k.startswith(big_prefixes)}
+    big = [k for k in arrays if k.startswith(big_prefixes)]
     parts, cur = [], {}
 
     def size_of(d):
@@ -46,7 +47,7 @@ def split(arrays, out_dir):
     if cur:
         parts.append(cur)
     small["meta.n_parts"] = np.int64(len(parts))
-    files = [(NAME + ".npz", small)] + [(f"{NAME}.part{i}.npz", p) for i, p in enumerate(parts)]
+    files = [(name + ".npz", small)] + [(f"{name}.part{i}.npz", p) for i, p in enumerate(parts)]
     for fn, d in files:
         path = os.path.join(out_dir, fn)
         np.savez_compressed(path, **d)
