@@ -357,6 +357,21 @@ def load():
     return lib
 
 
+# probe entry points (include/dr4sr_hip_probes.h): device primitives run on their own, for tests/.  Bound on first use, not in load(): a
+# library built before they existed must still load through DR4SR_LIB_PATH
+LANE_PROBE_NAMES = ("group16_sum", "group8_sum", "wave_sum", "xg_max", "xg_sum", "fold", "xor1")      # DR4SR_LP_*
+PROBE_SYMBOLS = {
+    "dr4sr_lane_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+}
+
+
+def probe(name: str):
+    """a typed probe entry point of the loaded library; raises if the library does not export it"""
+    fn = getattr(load(), name)           # AttributeError if the symbol is not exported
+    fn.restype, fn.argtypes = PROBE_SYMBOLS[name]
+    return fn
+
+
 _ERR = {-1: "DR4SR_E_ARG (null pointer / bad size)", -2: "DR4SR_E_SHAPE (unsupported D/H/F/L)",
         -3: "DR4SR_E_WS (workspace too small)"}
 

@@ -43,8 +43,9 @@ struct Lds {
     }
 };
 
-__device__ __forceinline__ float xg_max(float v) { return fmaxf(fmaxf(v, __shfl_xor(v, 16, 64)), fmaxf(__shfl_xor(v, 32, 64), __shfl_xor(v, 48, 64))); }
-__device__ __forceinline__ float xg_sum(float v) { v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64); return v; }
+// over the four lanes (i16, g = 0..3) of a query row; DPP (d = 64): permlane swaps, no LDS round trip (common.h)
+template <bool DPP> __device__ __forceinline__ float xg_max(float v) { if constexpr (DPP) return xrow_max(v); else return xrow_max_ref(v); }
+template <bool DPP> __device__ __forceinline__ float xg_sum(float v) { if constexpr (DPP) return xrow_sum(v); else return xrow_sum_ref(v); }
 
 // rows of one operand: lane (r16, g) reads DH / 4 contiguous floats of row (row0 + r16) at column col0 + g * DH / 4
 template <int DH>
@@ -290,14 +291,14 @@ __device__ __forceinline__ Keep fwd_compute(const PostArgs& P, const int t0, con
         }
     }
     TSTAMP(10, 0);
-    m = xg_max(m);
+    m = xg_max<D == 64>(m);
     float sum = 0.f;
 #pragma unroll
     for (int jt = 0; jt < MT; ++jt)
         if (jt >= jt_lo)
 #pragma unroll
             for (int r = 0; r < 4; ++r) { const float e = __expf(s[jt][r] - m); s[jt][r] = e; sum += e; }
-    sum = xg_sum(sum);
+    sum = xg_sum<D == 64>(sum);
     const float inv = 1.0f / sum;
     if (half == 0 && g == 0) {
         if (qok) { float* st = A.stat + ((size_t)tq * H + h) * 2; st[0] = m; st[1] = inv; }

@@ -163,6 +163,87 @@ __device__ __forceinline__ int find_seq_from(const int* __restrict__ cu, int B, 
 }
 
 // ---------------------------------------------------------------------------------- reductions
+// Butterfly reductions over the lanes of a wave WITHOUT LDS traffic.  __shfl_xor compiles to ds_bpermute_b32 + s_waitcnt lgkmcnt(0): an LDS
+// round trip (~50 cycles issue to use with one wave per SIMD) per step of a chain that is dependent by construction.  The forms below pair
+// the SAME two values at every step as `v = op(v, v[lane ^ o])`, so their results are bitwise those of the shuffle forms (beneath; the probe kernel k_lane_probe of probe.hip runs both; NaN payloads are the one thing not held equal):
+//   - inside a 16-lane group (a DPP row: lanes 16 k .. 16 k + 15; threadIdx.x & 15 is the column group everywhere) a step is a DPP row
+//     rotation.  After the step of offset 2 o a value depends on the lane index mod 2 o only — w[i] == w[i ^ 2 o], fp32 add is commutative —,
+//     and (i - o) mod 16 == (i ^ o) mod 2 o, so `row_ror:o` delivers the operand that `xor o` delivers.  The first step (o = 8) IS xor 8;
+//   - across rows, xor 16 is v_permlane16_swap of v with itself (odd rows of one copy <-> even rows of the other: every lane ends up holding its
+//     own value in one result and lane ^ 16's in the other) and xor 32 is v_permlane32_swap likewise (gfx950).  Which of the two results is
+//     "own" depends on the row, so op(r0, r1) has its operands swapped in half of the lanes: add, max and or are commutative;
+//   - an 8-lane group's first step (xor 4, values still distinct) takes a row shift left and a row shift right by 4 under complementary bank
+//     masks; its steps 2 and 1 are quad permutes, which are xor exactly.
+// All lanes of the reduced group must be active (as for the shuffles).  The builtins, not inline assembly: the compiler then places the two
+// wait states a DPP / permlane read of a fresh VALU result needs.
+#define DR4SR_DPP_ROW_SHL(n) (0x100 + (n))
+#define DR4SR_DPP_ROW_SHR(n) (0x110 + (n))
+#define DR4SR_DPP_ROW_ROR(n) (0x120 + (n))
+#define DR4SR_DPP_QUAD(a, b, c, d) ((a) | ((b) << 2) | ((c) << 4) | ((d) << 6))
+template <int CTRL>
+__device__ __forceinline__ float dpp_f32(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false)); }
+__device__ __forceinline__ uint32_t lane_xor1_u32(uint32_t v) {          // v[lane ^ 1]
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, DR4SR_DPP_QUAD(1, 0, 3, 2), 0xf, 0xf, false);
+}
+__device__ __forceinline__ float lane_xor4_f32(float v) {                // v[lane ^ 4]: banks 0, 2 read four lanes up, banks 1, 3 four lanes down
+    int t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), DR4SR_DPP_ROW_SHL(4), 0xf, 0x5, false);
+    t = __builtin_amdgcn_update_dpp(t, __float_as_int(v), DR4SR_DPP_ROW_SHR(4), 0xf, 0xa, false);
+    return __int_as_float(t);
+}
+struct LanePair { float a, b; };                                          // {v, v[lane ^ o]} in an order that depends on the row
+__device__ __forceinline__ LanePair lane_xor16_pair(float v) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return {__uint_as_float(r[0]), __uint_as_float(r[1])};
+}
+__device__ __forceinline__ LanePair lane_xor32_pair(float v) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return {__uint_as_float(r[0]), __uint_as_float(r[1])};
+}
+__device__ __forceinline__ float group16_sum_dpp(float v) {
+    v += dpp_f32<DR4SR_DPP_ROW_ROR(8)>(v);
+    v += dpp_f32<DR4SR_DPP_ROW_ROR(4)>(v);
+    v += dpp_f32<DR4SR_DPP_ROW_ROR(2)>(v);
+    v += dpp_f32<DR4SR_DPP_ROW_ROR(1)>(v);
+    return v;
+}
+__device__ __forceinline__ float group8_sum(float v) {
+    v += lane_xor4_f32(v);
+    v += dpp_f32<DR4SR_DPP_QUAD(2, 3, 0, 1)>(v);
+    v += dpp_f32<DR4SR_DPP_QUAD(1, 0, 3, 2)>(v);
+    return v;
+}
+// the four rows of a wave: v[l] + v[l ^ 16], then + the same of l ^ 32 (tattn::xg_sum, flush_affine's fold)
+__device__ __forceinline__ float xrow_sum(float v) {
+    const LanePair p = lane_xor16_pair(v); v = p.a + p.b;
+    const LanePair q = lane_xor32_pair(v); v = q.a + q.b;
+    return v;
+}
+// max(max(v, v[l ^ 16]), max(v[l ^ 32], v[l ^ 48])): lane l ^ 32's first-step result is the second operand
+__device__ __forceinline__ float xrow_max(float v) {
+    const LanePair p = lane_xor16_pair(v); v = fmaxf(p.a, p.b);
+    const LanePair q = lane_xor32_pair(v); v = fmaxf(q.a, q.b);
+    return v;
+}
+__device__ __forceinline__ float wave_sum_dpp(float v) {
+    const LanePair q = lane_xor32_pair(v); v = q.a + q.b;
+    const LanePair p = lane_xor16_pair(v); v = p.a + p.b;
+    return group16_sum_dpp(v);
+}
+// LPT lanes per token (the scorers: LPT = D / 4; 16 at d = 64, the DPP form)
+template <int LPT>
+__device__ __forceinline__ float lane_group_sum(float v) {
+    if constexpr (LPT == 16) return group16_sum_dpp(v);
+    else {
+#pragma unroll
+        for (int o = LPT / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        return v;
+    }
+}
+
+// The shuffle forms.  wave_sum and group16_sum remain the shared primitives of every kernel outside the d = 64 latency forms of linear.hip /
+// attn_tile.h: where their argument is a bare product (fmlp.hip's scorer, meta.hip) the compiler contracts the first butterfly add with it
+// into an fma, which the DPP / permlane forms do not reproduce — swapping the primitive under such a site changes result bits.  The others
+// (*_ref) are the probe kernel's references and the d = 128 instantiations' forms.
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -173,6 +254,16 @@ __device__ __forceinline__ float group16_sum(float v) {
     for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+template <bool DPP>
+__device__ __forceinline__ float group16_sum_sel(float v) { if constexpr (DPP) return group16_sum_dpp(v); else return group16_sum(v); }
+__device__ __forceinline__ float group8_sum_ref(float v) {
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float xrow_sum_ref(float v) { v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64); return v; }
+__device__ __forceinline__ float xrow_max_ref(float v) { return fmaxf(fmaxf(v, __shfl_xor(v, 16, 64)), fmaxf(__shfl_xor(v, 32, 64), __shfl_xor(v, 48, 64))); }
+__device__ __forceinline__ uint32_t lane_xor1_u32_ref(uint32_t v) { return (uint32_t)__shfl_xor((int)v, 1, 64); }
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
@@ -605,25 +696,26 @@ __device__ __forceinline__ void load_tile(float* __restrict__ As, int lda, const
 }
 
 // LayerNorm statistics of one row held as NV float4 per lane across a 16-lane group (D = 64*NV)
-template <int NV>
+// DPP: the lane sums by DPP row rotations (group16_sum_dpp) — the d = 64 latency forms
+template <int NV, bool DPP = false>
 __device__ __forceinline__ void ln_stats16(const float4 (&v)[NV], float& mean, float& rstd, float eps) {
     constexpr float invD = 1.0f / (64 * NV);
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; ++j) s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
-    mean = group16_sum(s) * invD;
+    mean = group16_sum_sel<DPP>(s) * invD;
     float q = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
         const float a = v[j].x - mean, b = v[j].y - mean, c = v[j].z - mean, d = v[j].w - mean;
         q += (a * a + b * b) + (c * c + d * d);
     }
-    rstd = 1.0f / sqrtf(group16_sum(q) * invD + eps);
+    rstd = 1.0f / sqrtf(group16_sum_sel<DPP>(q) * invD + eps);
 }
 
 // LayerNorm backward of one row spread over a 16-lane group.  dzv: upstream grad, uv: LN input.
 // Returns du in dzv; accumulates affine partials.
-template <int NV>
+template <int NV, bool DPP = false>
 __device__ __forceinline__ void ln_bwd_row(float4 (&dzv)[NV], const float4 (&uv)[NV], float mean, float rstd,
                                            const float4 (&gam)[NV], float4 (&dgam)[NV], float4 (&dbet)[NV]) {
     constexpr float invD = 1.0f / (64 * NV);
@@ -638,8 +730,8 @@ __device__ __forceinline__ void ln_bwd_row(float4 (&dzv)[NV], const float4 (&uv)
         dgam[j].x += dzv[j].x * xh[j].x; dgam[j].y += dzv[j].y * xh[j].y; dgam[j].z += dzv[j].z * xh[j].z; dgam[j].w += dzv[j].w * xh[j].w;
         dbet[j].x += dzv[j].x; dbet[j].y += dzv[j].y; dbet[j].z += dzv[j].z; dbet[j].w += dzv[j].w;
     }
-    s1 = group16_sum(s1) * invD;
-    s2 = group16_sum(s2) * invD;
+    s1 = group16_sum_sel<DPP>(s1) * invD;
+    s2 = group16_sum_sel<DPP>(s2) * invD;
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
         dzv[j].x = rstd * (g[j].x - s1 - xh[j].x * s2);

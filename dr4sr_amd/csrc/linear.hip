@@ -419,7 +419,7 @@ __device__ __forceinline__ void ln_rowpass(const float* __restrict__ Cs, int ldc
         }
     }
 #pragma unroll
-    for (int ps = 0; ps < PASSES; ++ps) ln_stats16<NV>(v[ps], mean[ps], rstd[ps], eps);
+    for (int ps = 0; ps < PASSES; ++ps) ln_stats16<NV, NV == 1>(v[ps], mean[ps], rstd[ps], eps);
     if constexpr (CARRY) { cy->v = v[0][0]; cy->mean = mean[0]; cy->rstd = rstd[0]; }
 #pragma unroll
     for (int ps = 0; ps < PASSES; ++ps) {
@@ -460,7 +460,7 @@ __device__ __forceinline__ uint32_t row_keep_word(const RngKey& rk, const uint32
     const uint32_t b1 = actdrop ? drop_bits8(rk, sA, (uint64_t)t * F + (odd ? 64 : 0) + 8 * pr) : 0xffu;
     const uint32_t own0 = odd ? b0 >> 4 : b0 & 15u, own1 = odd ? b1 >> 4 : b1 & 15u;
     const uint32_t give = odd ? (b0 & 15u) | ((b1 & 15u) << 4) : (b0 >> 4) | (b1 & 0xf0u);
-    const uint32_t got = (uint32_t)__shfl_xor((int)give, 1, 64), got0 = got & 15u, got1 = got >> 4;
+    const uint32_t got = lane_xor1_u32(give), got0 = got & 15u, got1 = got >> 4;
     return odd ? got0 | (own0 << 4) | (got1 << 8) | (own1 << 12) : own0 | (got0 << 4) | (own1 << 8) | (got1 << 12);
 }
 // KU (host: row_keep_saved; 16-row tiles, d = 64, F = 128, training with dropout, CARRY 1 | 2): the three row passes take their keep decisions
@@ -662,11 +662,13 @@ __global__ __launch_bounds__(256) void k_post_fwd(const PostArgs A) {
 // fold the 16 row-groups of the workgroup (4 per wave x 4 waves) into ONE partial row per token tile:
 // dst[0..D) = sum dgam, dst[D..2D) = sum dbet.  `scr` is a [4 waves][2*D] LDS scratch.  Deterministic, no atomics;
 // the tile partials are summed by k_wgrad's reduce job.
-template <int NV>
+// DPP: the fold over the wave's four rows by permlane swaps (the d = 64 latency forms; every other form keeps the shuffles — FMLP's
+// Intermediate LayerNorm gradient came out with other low bits under the swaps)
+template <int NV, bool DPP = false>
 __device__ __forceinline__ void flush_affine(const float4 (&dgam)[NV], const float4 (&dbet)[NV], float* scr, float* dst) {
     constexpr int D = 64 * NV;
     const int l16 = threadIdx.x & 15, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    auto fold = [&](float v) { v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64); return v; };
+    auto fold = [&](float v) { if constexpr (DPP) return xrow_sum(v); else return xrow_sum_ref(v); };
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
         const int c = 4 * l16 + 64 * j;
@@ -729,7 +731,7 @@ __device__ __forceinline__ void ln_bwd_rowpass(const float* __restrict__ Gg, con
         }
     }
 #pragma unroll
-    for (int ps = 0; ps < PASSES; ++ps) ln_bwd_row<NV>(g[ps], u[ps], mean[ps], rstd[ps], gam, dgam, dbet);
+    for (int ps = 0; ps < PASSES; ++ps) ln_bwd_row<NV, NV == 1>(g[ps], u[ps], mean[ps], rstd[ps], gam, dgam, dbet);
 #pragma unroll
     for (int ps = 0; ps < PASSES; ++ps) {
         const int row = ps * 16 + rsub, t = t0 + row;
@@ -890,7 +892,7 @@ __device__ __forceinline__ void post_bwd_body(const PostArgs& A, const int t0, c
         ln_bwd_rowpass<BM, D, 0, CARRY>(A.dz, nullptr, nullptr, LD, A.u2, A.st2, A.ln2_w, nullptr, R1, A.df, R0, dgam, dbet, t0, T, dodrop, rk, sF, nullptr,
                                         CARRY ? &cy->ln2 : nullptr);
     }
-    flush_affine<NV>(dgam, dbet, R2, A.ln_part + (size_t)tile * 4 * D);
+    flush_affine<NV, NV == 1 && BM == 16 && !FFN_ONLY>(dgam, dbet, R2, A.ln_part + (size_t)tile * 4 * D);
     // ---- dh = df W2   (x W^T form with W2^T [F][D])
     {
         TileAcc<BM, F> acc;
@@ -948,7 +950,7 @@ __device__ __forceinline__ void post_bwd_body(const PostArgs& A, const int t0, c
     }
     ln_bwd_rowpass<BM, D, 1, CARRY>(nullptr, R0, R1, LD, A.u1, A.st1, A.ln1_w, A.du1, nullptr, A.dout, R1, dgam, dbet, t0, T, dodrop, rk, sP, nullptr,
                                     CARRY ? &cy->ln1 : nullptr);
-    flush_affine<NV>(dgam, dbet, R2, A.ln_part + (size_t)tile * 4 * D + 2 * D);
+    flush_affine<NV, NV == 1 && BM == 16 && !FFN_ONLY>(dgam, dbet, R2, A.ln_part + (size_t)tile * 4 * D + 2 * D);
     // ---- dctx = do W_out
     {
         TileAcc<BM, D> acc;
@@ -969,7 +971,8 @@ __device__ __forceinline__ void post_bwd_body(const PostArgs& A, const int t0, c
             float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
             if (ok) o = ld4(A.ctx + (size_t)(t0 + row) * D + c);
             float d = (v.x * o.x + v.y * o.y) + (v.z * o.z + v.w * o.w);
-            for (int off = lph >> 1; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
+            if (D == 64 && lph == 8) d = group8_sum(d);          // (n_head = 2 at d = 64, the headline shape: DPP, no LDS round trips — common.h)
+            else for (int off = lph >> 1; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
             if (ok && (i % C4) % lph == 0) A.rd[(size_t)(t0 + row) * A.n_head + (i % C4) / lph] = d;
             if constexpr (AT) { if (at_on && (i % C4) % lph == 0) tattn::Lds<D>(smem + att_lds_off(D, F)).rd[row * 2 + (i % C4) / lph] = d; }
         }
@@ -1002,12 +1005,7 @@ __global__ __launch_bounds__(256) void k_post_bwd(const PostArgs A) {
 // products by lane-group shuffles, un-normalised dz + table-gradient atomics; the tile's (count, loss) partial goes to
 // part[2*tile] (summed by k_wgrad's reduce job).  Valid targets at positions >= seqlen (query row is zero there) are
 // counted by the sequence's last token, as the per-sequence scorer does.
-template <int LPT>
-__device__ __forceinline__ float lane_group_sum(float v) {
-#pragma unroll
-    for (int o = LPT / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+// (lane_group_sum<LPT>: common.h)
 
 // MetaModel.selection for ONE token inside the scorer (D = 64: 16 lanes per token, lane l holds z[4l..4l+3] and owns hidden units
 // 4l..4l+3 of the 64->64->2 MLP; W1 is read from L1/L2 — phi is 17 KB).  Returns weight_t and, in dzw, loss_t * d weight_t / d z
@@ -1429,7 +1427,7 @@ __device__ __forceinline__ void score_tile_regs(const PostArgs& A, const ScoreTi
         dzreg[ps][0] = dz;
     }
     // workgroup reduction of (cnt, lsum) -> one partial per tile; `red` is scratch no tile region overlaps
-    cnt = wave_sum(cnt); lsum = wave_sum(lsum);
+    cnt = wave_sum_dpp(cnt); lsum = wave_sum_dpp(lsum);
     if ((threadIdx.x & 63) == 0) { red[2 * (threadIdx.x >> 6)] = cnt; red[2 * (threadIdx.x >> 6) + 1] = lsum; }
     lds_barrier();
     if (threadIdx.x == 0) {
