@@ -669,6 +669,53 @@ __device__ __forceinline__ void tile_to_global(const TileAcc<BM, N>& t, float* _
     }
 }
 
+// The same two epilogues with the bias of this thread's columns as VALUES (bias_cols_load): the 16-row d = 64 latency forms request every
+// parameter vector at kernel entry, in front of the fragment requests and of the row passes' stores — vector memory operations retire in
+// issue order, so a bias requested inside the epilogue waits for every store and fragment request issued before it.
+// the forms that do (-DDR4SR_NO_ENTRY_PARAMS: none — the loads-in-place build for A / B runs)
+__host__ __device__ constexpr bool entry_params(int BM, int D, bool FFN_ONLY) {
+#ifdef DR4SR_NO_ENTRY_PARAMS
+    return false;
+#else
+    return BM == 16 && D == 64 && !FFN_ONLY;
+#endif
+}
+template <int N>
+__device__ __forceinline__ void bias_cols_load(float (&bv)[N / 64], const float* __restrict__ bias) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r16 = lane & 15;
+#pragma unroll
+    for (int i = 0; i < N / 64; ++i) bv[i] = bias[(w + 4 * i) * 16 + r16];
+}
+template <int BM, int N>
+__device__ __forceinline__ void tile_to_lds(const TileAcc<BM, N>& t, float* __restrict__ Cs, int ldc, const float (&bv)[N / 64]) {
+    static_assert(BM == 16 || BM == 32, "the 16x16x4 accumulator layout");
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r16 = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int i = 0; i < N / 64; ++i) {
+        const int col = (w + 4 * i) * 16 + r16;
+#pragma unroll
+        for (int r = 0; r < BM / 16; ++r)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) Cs[(r * 16 + 4 * g + q) * ldc + col] = t.a[r][i][q] + bv[i];
+    }
+}
+template <int BM, int N>
+__device__ __forceinline__ void tile_to_global(const TileAcc<BM, N>& t, float* __restrict__ C, int ldc, const float (&bv)[N / 64], int t0, int T) {
+    static_assert(BM == 16 || BM == 32, "the 16x16x4 accumulator layout");
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r16 = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int i = 0; i < N / 64; ++i) {
+        const int col = (w + 4 * i) * 16 + r16;
+#pragma unroll
+        for (int r = 0; r < BM / 16; ++r)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int tt = t0 + r * 16 + 4 * g + q;
+                if (tt < T) C[(size_t)tt * ldc + col] = t.a[r][i][q] + bv[i];
+            }
+    }
+}
+
 // cooperative load of a [BM x K] tile (rows t0.. of a [T x ldg] global matrix, zero beyond T) into LDS, row stride lda
 template <int BM, int K>
 __device__ __forceinline__ void load_tile_bm(float* __restrict__ As, int lda, const float* __restrict__ G, int ldg, int t0, int T) {

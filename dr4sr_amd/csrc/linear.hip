@@ -286,6 +286,9 @@ __global__ __launch_bounds__(256) void k_embqkv_fwd(const EmbQkvArgs A) {
     // latency regime: the in_proj fragments are requested in front of the gather's dependent chain (cu -> idx -> table row)
     constexpr bool PFE = BM == 16 && D == 64;
     WFragT<PFE ? D : 16, PFE ? N : 64> f_in;
+    float in_b[N / 64];                        // ... and the bias of this thread's epilogue columns with them (DR4SR_NO_ENTRY_PARAMS: in the epilogue)
+    constexpr bool EPB = PFE && entry_params(BM, D, false);
+    if constexpr (EPB) bias_cols_load<N>(in_b, A.bias);
     if constexpr (PFE) wfrag_load(f_in, A.W, D);
     const int bh = A.tile_seq[t0 >> 4];
 #pragma unroll
@@ -317,7 +320,7 @@ __global__ __launch_bounds__(256) void k_embqkv_fwd(const EmbQkvArgs A) {
     tile_zero(acc);
     if constexpr (PFE) tile_mma_frag<BM, D, N>(As, LDA, f_in, acc);
     else tile_gemm<D == 128 && BM == 32, BM, D, N>(As, LDA, A.W, D, false, A.sp, WSplitGeo<D, 128>::E, 0, acc);
-    tile_to_global<BM, N>(acc, A.QKV, N, A.bias, t0, T);
+    if constexpr (EPB) tile_to_global<BM, N>(acc, A.QKV, N, in_b, t0, T); else tile_to_global<BM, N>(acc, A.QKV, N, A.bias, t0, T);
     if (A.dqkv_zero) zero_kv_rows<BM, D>(A.dqkv_zero, t0, T);
 }
 
@@ -381,21 +384,27 @@ __device__ __forceinline__ float4 keep_factors4(const RngKey& k, uint32_t bits) 
 //   KPRE (with CARRY): the keep bits ARRIVE in cy->keep (row_keep_word below) — no Philox call here —, and a residual row in global memory
 //   arrives in cy->v (requested at kernel entry)
 //   NOST (with CARRY): U and ST are not stored — the only reader is the backward half of the same launch, from *cy (k_post_mid<16, 64, ...>)
-template <int BM, int D, bool RES_IN_LDS, bool COPY_LDS, bool CARRY = false, bool KPRE = false, bool NOST = false>
+//   GPRE: gamma and beta of this thread's float4 ARRIVE in gb[0] / gb[1] (EntryParams below) — no load behind the barrier in front of the pass
+template <int BM, int D, bool RES_IN_LDS, bool COPY_LDS, bool CARRY = false, bool KPRE = false, bool NOST = false, bool GPRE = false>
 __device__ __forceinline__ void ln_rowpass(const float* __restrict__ Cs, int ldc, const float* res, int ldres,
                                            const float* __restrict__ lnw, const float* __restrict__ lnb, float eps,
                                            float* __restrict__ U, float* __restrict__ OUT, float* __restrict__ ST,
                                            float* Ls, int ldl, int t0, int T, bool dodrop, const RngKey& rk,
-                                           uint32_t site, float4 (*yreg)[D / 64] = nullptr, LnCarry* cy = nullptr) {
+                                           uint32_t site, float4 (*yreg)[D / 64] = nullptr, LnCarry* cy = nullptr,
+                                           const float4* gb = nullptr) {
     constexpr int NV = D / 64, PASSES = BM / 16;
     static_assert(!CARRY || (NV == 1 && PASSES == 1), "the carried row state is one float4 per thread");
+    static_assert(!GPRE || NV == 1, "gamma and beta arrive as one float4 each");
     static_assert(!KPRE || CARRY, "the keep bits arrive in the carried row state");
     static_assert(!NOST || CARRY, "the row state leaves through *cy only");
     const int l16 = threadIdx.x & 15, rsub = threadIdx.x >> 4;
     float4 gam[NV], bet[NV], v[PASSES][NV];
     float mean[PASSES], rstd[PASSES];
 #pragma unroll
-    for (int j = 0; j < NV; ++j) { gam[j] = ld4(lnw + 4 * l16 + 64 * j); bet[j] = ld4(lnb + 4 * l16 + 64 * j); }
+    for (int j = 0; j < NV; ++j) {
+        if constexpr (GPRE) { gam[j] = gb[0]; bet[j] = gb[1]; }
+        else { gam[j] = ld4(lnw + 4 * l16 + 64 * j); bet[j] = ld4(lnb + 4 * l16 + 64 * j); }
+    }
 #pragma unroll
     for (int ps = 0; ps < PASSES; ++ps) {
         const int row = ps * 16 + rsub, t = t0 + row;
@@ -463,6 +472,19 @@ __device__ __forceinline__ uint32_t row_keep_word(const RngKey& rk, const uint32
     const uint32_t got = lane_xor1_u32(give), got0 = got & 15u, got1 = got >> 4;
     return odd ? got0 | (own0 << 4) | (got1 << 8) | (own1 << 12) : own0 | (got0 << 4) | (own1 << 8) | (got1 << 12);
 }
+// The parameter vectors of the forward body of a 16-row d = 64 token tile, requested ONCE at kernel entry (entry_params, common.h: every
+// k_post_fwd / k_post_mid instantiation with BM = 16, D = 64 and attention, and k_embqkv_fwd<16, 64>'s bias; the 32- / 64-row forms, d = 128 and
+// the FFN-only forms load them where they are consumed).  Vector loads, stores and atomics share one counter and retire in issue order: a
+// bias requested in a GEMM epilogue, or gamma / beta at the head of a row pass, waits for every store of the row pass in front of it and for
+// the weight-fragment requests still in flight — and, as compiled, every row store of the next in_proj's epilogue waited for the one before
+// it (a vmcnt(0) per store, left by the bias load of a branch).  Requested first they are a few hundred bytes per wave and return first.
+// The epilogue columns are tile_to_lds's ((w + 4 i) 16 + r16), the float4 is the row passes' (4 (threadIdx.x & 15)): 7 + 16 registers.
+// NOT the backward body's gamma: measured no gain (k_post_bwd -0.08 us, the step equal), and with gamma known ahead of the scorer the compiler
+// fuses the products dz * gamma of k_post_mid differently — other low bits than the parent's in deterministic mode.  NOTEBOOK.
+template <int D, int F>
+struct EntryParams { float out_b[D / 64], b1[F / 64], b2[D / 64], nx_b[3 * D / 64]; float4 ln1[2], ln2[2]; };      // ln: {gamma, beta}
+struct NoEntryParams {};
+
 // KU (host: row_keep_saved; 16-row tiles, d = 64, F = 128, training with dropout, CARRY 1 | 2): the three row passes take their keep decisions
 // from ONE word computed ahead of them (row_keep_word: two Philox calls per thread instead of four, none inside the GELU and LayerNorm2 passes,
 // which touch no global memory and hide nothing), and LayerNorm1's residual row is requested at kernel entry.
@@ -488,6 +510,15 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
     WFragT<PF ? F : 16, PF ? D : 64> f_w2;
     WFragT<PF ? D : 16, PF ? 3 * D : 64> f_nx;
     STAMP(0);
+    constexpr bool EP = entry_params(BM, D, FFN_ONLY);
+    std::conditional_t<EP, EntryParams<D, F>, NoEntryParams> ep;
+    if constexpr (EP) {                        // in front of the window and of every fragment request
+        bias_cols_load<D>(ep.out_b, A.out_b); bias_cols_load<F>(ep.b1, A.b1); bias_cols_load<D>(ep.b2, A.b2);
+        if (A.nx_qkv) bias_cols_load<3 * D>(ep.nx_b, A.nx_in_b);
+        ep.ln1[0] = ld4(A.ln1_w + 4 * l16); ep.ln1[1] = ld4(A.ln1_b + 4 * l16);
+        ep.ln2[0] = ld4(A.ln2_w + 4 * l16); ep.ln2[1] = ld4(A.ln2_b + 4 * l16);
+        __builtin_amdgcn_sched_barrier(0);
+    }
     static_assert(!KU || (BM == 16 && D == 64 && F == 128 && !FFN_ONLY && CARRY != 0), "one row, one float4, 16 keep bits per thread");
     // CARRY 1: the backward half of the same launch takes u1 / st1 / a / u2 / st2 from *cy and no other launch reads them (the fused step
     // runs no k_post_bwd of this layer; k_wgrad reads y, h, ctx, x) — they are not stored, and A holds null pointers for them
@@ -571,12 +602,14 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
             tile_zero(acc);
             if constexpr (PF) tile_mma_frag<BM, D, D>(R0, LD, f_out, acc);
             else tile_gemm<BM == 32 && (D == 128 || FFN_ONLY), BM, D, D>(R0, LD, A.out_w, D, false, A.sp, WSplitGeo<D, F>::E, WSplitGeo<D, F>::OUT, acc);
-            tile_to_lds<BM, D>(acc, R2, LD, A.out_b);
+            if constexpr (EP) tile_to_lds<BM, D>(acc, R2, LD, ep.out_b); else tile_to_lds<BM, D>(acc, R2, LD, A.out_b);
         }
         lds_barrier(); STAMP(2);
         if constexpr (KU && !KU_EARLY) keep_upfront();
         // ---- dropout1 + residual + LayerNorm1
-        ln_rowpass<BM, D, false, true, CARRY != 0, KU, NOST>(R2, LD, A.x, D, A.ln1_w, A.ln1_b, A.eps, A.u1, A.y, A.st1, R1, LD, t0, T, dodrop, rk, sP, nullptr,
+        if constexpr (EP) ln_rowpass<BM, D, false, true, CARRY != 0, KU, NOST, EP>(R2, LD, A.x, D, A.ln1_w, A.ln1_b, A.eps, A.u1, A.y, A.st1, R1, LD, t0, T, dodrop, rk, sP, nullptr,
+                                                  CARRY ? &cy->ln1 : nullptr, ep.ln1);
+        else ln_rowpass<BM, D, false, true, CARRY != 0, KU, NOST>(R2, LD, A.x, D, A.ln1_w, A.ln1_b, A.eps, A.u1, A.y, A.st1, R1, LD, t0, T, dodrop, rk, sP, nullptr,
                                                   CARRY ? &cy->ln1 : nullptr);
     }
     lds_barrier(); STAMP(3);
@@ -586,7 +619,7 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
         tile_zero(acc);
         if constexpr (PF) tile_mma_frag<BM, D, F>(R1, LD, f_w1, acc);
         else tile_gemm<BM == 32 && (D == 128 || FFN_ONLY), BM, D, F>(R1, LD, A.w1, D, false, A.sp, WSplitGeo<D, F>::E, WSplitGeo<D, F>::W1, acc);
-        tile_to_lds<BM, F>(acc, R2, LF, A.b1);
+        if constexpr (EP) tile_to_lds<BM, F>(acc, R2, LF, ep.b1); else tile_to_lds<BM, F>(acc, R2, LF, A.b1);
     }
     lds_barrier(); STAMP(4);
     {
@@ -623,11 +656,13 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
         tile_zero(acc);
         if constexpr (PF) tile_mma_frag<BM, F, D>(R2, LF, f_w2, acc);
         else tile_gemm<BM == 32 && (D == 128 || FFN_ONLY), BM, F, D>(R2, LF, A.w2, F, false, A.sp, WSplitGeo<D, F>::E, WSplitGeo<D, F>::W2, acc);
-        tile_to_lds<BM, D>(acc, R0, LD, A.b2);
+        if constexpr (EP) tile_to_lds<BM, D>(acc, R0, LD, ep.b2); else tile_to_lds<BM, D>(acc, R0, LD, A.b2);
     }
     lds_barrier(); STAMP(6);
     if (!FFN_ONLY && A.nx_qkv) {               // layer-boundary fusion: keep z in LDS and emit the next layer's in_proj
-        ln_rowpass<BM, D, true, true, CARRY != 0, KU, NOST>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, R1, LD, t0, T, dodrop, rk, sF, nullptr,
+        if constexpr (EP) ln_rowpass<BM, D, true, true, CARRY != 0, KU, NOST, EP>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, R1, LD, t0, T, dodrop, rk, sF, nullptr,
+                                                  CARRY ? &cy->ln2 : nullptr, ep.ln2);
+        else ln_rowpass<BM, D, true, true, CARRY != 0, KU, NOST>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, R1, LD, t0, T, dodrop, rk, sF, nullptr,
                                                   CARRY ? &cy->ln2 : nullptr);
         if constexpr (CARRY == 2) row_keep_store<F>(A, *cy, t0, T);
         lds_barrier();
@@ -635,10 +670,12 @@ __device__ __forceinline__ void post_fwd_body(const PostArgs& A, const int t0, c
         tile_zero(acc);
         if constexpr (PF) tile_mma_frag<BM, D, 3 * D>(R1, LD, f_nx, acc);
         else tile_gemm<BM == 32 && (D == 128 || FFN_ONLY), BM, D, 3 * D>(R1, LD, A.nx_in_w, D, false, A.sp ? A.sp + 4 * WSplitGeo<D, F>::E : nullptr, WSplitGeo<D, F>::E, 0, acc);
-        tile_to_global<BM, 3 * D>(acc, A.nx_qkv, 3 * D, A.nx_in_b, t0, T);
+        if constexpr (EP) tile_to_global<BM, 3 * D>(acc, A.nx_qkv, 3 * D, ep.nx_b, t0, T); else tile_to_global<BM, 3 * D>(acc, A.nx_qkv, 3 * D, A.nx_in_b, t0, T);
         if (A.nx_dqkv_zero) zero_kv_rows<BM, D>(A.nx_dqkv_zero, t0, T);
     } else {
-        ln_rowpass<BM, D, true, false, CARRY != 0, KU, NOST>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, nullptr, 0, t0, T, dodrop, rk, sF, zreg,
+        if constexpr (EP) ln_rowpass<BM, D, true, false, CARRY != 0, KU, NOST, EP>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, nullptr, 0, t0, T, dodrop, rk, sF, zreg,
+                                                   CARRY ? &cy->ln2 : nullptr, ep.ln2);
+        else ln_rowpass<BM, D, true, false, CARRY != 0, KU, NOST>(R0, LD, R1, LD, A.ln2_w, A.ln2_b, A.eps, A.u2, A.z, A.st2, nullptr, 0, t0, T, dodrop, rk, sF, zreg,
                                                    CARRY ? &cy->ln2 : nullptr);
         if constexpr (CARRY == 2) row_keep_store<F>(A, *cy, t0, T);
     }
@@ -754,14 +791,31 @@ __device__ __forceinline__ void ln_bwd_rowpass(const float* __restrict__ Gg, con
     }
 }
 
+// The scorer's table adds of one thread of k_post_mid<16, 64, ...> (score_tile_regs pass 2, atomics path): eight float adds into two rows of dE,
+// cold lines at random addresses.  Issued inside the scorer they stood in front of the backward half's first fragment request, and vector
+// loads, stores and atomics retire in issue order: the first backward GEMM waited for every add to be acknowledged.  The scorer fills this
+// record instead (gp == NULL: nothing to add) and post_bwd_body issues the adds behind the last load it waits for (the ctx rows of the rd
+// sum); the launch's remaining phase, the in-tile attention backward, reads LDS.  The products are the scorer's own (dpos * wt, dneg * wt
+// times the query float4).  -DDR4SR_ADDS_IN_SCORER builds the adds-in-place form for A / B runs.
+struct TableAdds {
+    float* gp; float* gn; float dpos, dneg; float4 q;
+    __device__ __forceinline__ void issue() const {
+        if (gp) {
+            unsafeAtomicAdd(gp, dpos * q.x); unsafeAtomicAdd(gp + 1, dpos * q.y); unsafeAtomicAdd(gp + 2, dpos * q.z); unsafeAtomicAdd(gp + 3, dpos * q.w);
+            unsafeAtomicAdd(gn, dneg * q.x); unsafeAtomicAdd(gn + 1, dneg * q.y); unsafeAtomicAdd(gn + 2, dneg * q.z); unsafeAtomicAdd(gn + 3, dneg * q.w);
+        }
+    }
+};
+
 // DET: the deterministic latency form (kernels.h Workspace::det_lat) — a separate instantiation: as a run-time branch it cost the default step
 // 0.8 % (d = 64) / 2 % (d = 128) at B = 256
 // CARRY (RowCarry above): 1 (k_post_mid<16, 64, ...>) the three row passes take their saved activations and keep decisions from *cy_in;
 // 2 | 3 (k_post_bwd<16, 64, ...>) this thread's u2 / st2 / a / u1 / st1 [and keep word: 3] are requested at kernel entry
+// ta (k_post_mid<16, 64, ...>): the scorer's table adds of this thread, issued behind the last load this body waits for (TableAdds)
 template <int BM, int D, int F, bool FFN_ONLY, bool DET = false, int CARRY = 0>
 __device__ __forceinline__ void post_bwd_body(const PostArgs& A, const int t0, const int T, const int tile,
                                               const float4 (*dzreg)[D / 64] = nullptr, const tattn::Keep* att_staged = nullptr,
-                                              const RowCarry<F>* cy_in = nullptr) {
+                                              const RowCarry<F>* cy_in = nullptr, const TableAdds* ta = nullptr) {
     constexpr int LD = D + 4, LF = F + 4, NV = D / 64, NVF = F / 64, PASSES = BM / 16;
     float* R1 = smem;                          // R1 first: R0 and R2 are contiguous and together hold a [64][3D+4] dqkv tile
     float* R0 = R1 + BM * LD;
@@ -977,6 +1031,11 @@ __device__ __forceinline__ void post_bwd_body(const PostArgs& A, const int t0, c
             if constexpr (AT) { if (at_on && (i % C4) % lph == 0) tattn::Lds<D>(smem + att_lds_off(D, F)).rd[row * 2 + (i % C4) / lph] = d; }
         }
     }
+    // the scorer's table adds (k_post_mid<16, 64, ...>): behind the LAST wait for a load of this launch — the ctx rows above; what follows
+    // (the in-tile attention backward) reads LDS and only stores and adds, so nothing waits for these adds before the launch ends.  Right
+    // behind out_proj's fragment request the last fragments of that GEMM and the ctx rows would still wait for them: the compiler counts
+    // the adds of a divergent branch as not issued, and its vmcnt(0) in front of the last fragment covers them (measured equal or slower)
+    if constexpr (PF64) { if (ta) { __builtin_amdgcn_sched_barrier(0); ta->issue(); __builtin_amdgcn_sched_barrier(0); } }
     if constexpr (AT) {
         if (at_on) {
             STAMP(17);
@@ -1269,9 +1328,11 @@ __device__ __forceinline__ void score_prefetch(const PostArgs& A, const ScoreTil
 // the workgroup's LDS tile instead of per-lane dot loops (each token's 16 lanes read all of W1 twice from L1: +11.5 us on the
 // 24 us launch at B = 256): pre = Z W1^T + b1 [BM x 64], then the per-token gate / softmax weight / d hidden, then dzw = dh W1.
 // `tile` points at two [BM][68] LDS tiles (the post kernels' regions are free between the two halves).
+// ta (16-row tiles): the table adds of the atomics path are not issued here but recorded for post_bwd_body (TableAdds)
 template <int BM, bool META>
 __device__ __forceinline__ void score_tile_regs(const PostArgs& A, const ScoreTileArgs& S, const int t0, const int T, const int tile,
-                                                const ScorePre<BM>& P, const float4 (*zreg)[1], float4 (*dzreg)[1], float* red, float* lds_tile) {
+                                                const ScorePre<BM>& P, const float4 (*zreg)[1], float4 (*dzreg)[1], float* red, float* lds_tile,
+                                                TableAdds* ta = nullptr) {
     int4* lrec = reinterpret_cast<int4*>(red + 8);        // [BM] the tile's records for tile_sort (S.ent), instead of S.rec in global memory
     constexpr int D = 64, LPT = 16, LD = D + 4, PASSES = ScorePre<BM>::PASSES;
     const int c = (threadIdx.x & 15) * 4, sub = threadIdx.x & 15;
@@ -1407,7 +1468,9 @@ __device__ __forceinline__ void score_tile_regs(const PostArgs& A, const ScoreTi
                                  dpos * ep.w + dneg * en.w + dzw.w);
                 float* gp = S.dE + tgt * D + c;
                 float* gn = S.dE + ng * D + c;
-                if (!S.rec) {
+                if (!S.rec && ta) {
+                    ta->gp = gp; ta->gn = gn; ta->dpos = dpos; ta->dneg = dneg; ta->q = q;
+                } else if (!S.rec) {
                     unsafeAtomicAdd(gp, dpos * q.x); unsafeAtomicAdd(gp + 1, dpos * q.y); unsafeAtomicAdd(gp + 2, dpos * q.z); unsafeAtomicAdd(gp + 3, dpos * q.w);
                     unsafeAtomicAdd(gn, dneg * q.x); unsafeAtomicAdd(gn + 1, dneg * q.y); unsafeAtomicAdd(gn + 2, dneg * q.z); unsafeAtomicAdd(gn + 3, dneg * q.w);
                 } else if (sub == 0) {                    // owner-computes mode: one 16-byte record per token, the table rows are summed by k_wgrad's owner job
@@ -1451,12 +1514,18 @@ __device__ __forceinline__ void post_mid_body(const PostArgs& A, const ScoreTile
         constexpr int CARRY = BM == 16 ? 1 : 0;              // latency regime: the row passes' state crosses the two halves in registers
         if constexpr (CARRY == 1) Af.u1 = Af.st1 = Af.a = Af.u2 = Af.st2 = nullptr;      // ... and nowhere else: the forward half does not store it
         RowCarry<F> cy;
+#ifdef DR4SR_ADDS_IN_SCORER
+        constexpr bool DEFER = false;                        // (A / B runs: the table adds where the scorer computes them)
+#else
+        constexpr bool DEFER = BM == 16;
+#endif
+        TableAdds ta{nullptr, nullptr, 0.f, 0.f, make_float4(0.f, 0.f, 0.f, 0.f)};
         post_fwd_body<BM, D, F, false, true, CARRY, KU>(Af, t0, T, zreg, &keep, &cy);
         if constexpr (BM != 16) score_prefetch<BM>(A, S, t0, T, P);             // occupancy regime: its registers would cost a workgroup per CU
         if constexpr (META) lds_barrier();                   // every wave is past the forward half's last LDS reads: the tiles are free
-        score_tile_regs<BM, META>(A, S, t0, T, bx, P, zreg, dzreg, smem + post_lds_floats(D, F, BM), smem);
+        score_tile_regs<BM, META>(A, S, t0, T, bx, P, zreg, dzreg, smem + post_lds_floats(D, F, BM), smem, DEFER ? &ta : nullptr);
         if constexpr (BM != 16) { if (S.ent) tile_sort<BM>(S, bx, t0, T, smem + post_lds_floats(D, F, BM) + 8); }
-        post_bwd_body<BM, D, F, false, DET, CARRY>(A, t0, T, bx, dzreg, &keep, &cy);
+        post_bwd_body<BM, D, F, false, DET, CARRY>(A, t0, T, bx, dzreg, &keep, &cy, DEFER ? &ta : nullptr);
     } else {
         tattn::Keep keep{0xffffffffu, 0xffffffffu};
         post_fwd_body<BM, D, F, false, true>(A, t0, T, nullptr, &keep);
