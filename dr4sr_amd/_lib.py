@@ -107,6 +107,11 @@ class SasrecPlan(C.Structure):
                 + _PLAN_PERM_LOG + _i32("expected_tokens", "optimizer"))
 
 
+class SasrecInputs(C.Structure):
+    """mirror of `dr4sr_sasrec_inputs` (include/dr4sr_hip.h): the encoder's optional per-token input scale and its gradient"""
+    _fields_ = [("input_weight", _f32p), ("d_input_weight", _f32p)]
+
+
 class MetaWeighting(C.Structure):
     """mirror of `dr4sr_meta_weighting` (include/dr4sr_hip.h)"""
     _fields_ = [("phi", _f32p), ("gumbel", _f32p), ("user_id", _i64p), ("gate_in", C.c_void_p), ("gate_out", C.c_void_p),
@@ -167,6 +172,8 @@ SYMBOLS = {
     "dr4sr_sasrec_fwd_bwd_phase": (C.c_int, [_PLANP, C.c_int32, C.c_int32, C.c_void_p]),
     "dr4sr_sasrec_encode": (C.c_int, [_PLANP, C.c_int32, C.c_int32, _f32p, C.c_void_p]),
     "dr4sr_sasrec_encode_bwd": (C.c_int, [_PLANP, C.c_int32, C.c_int32, _f32p, C.c_void_p]),
+    "dr4sr_sasrec_encode_w": (C.c_int, [_PLANP, C.POINTER(SasrecInputs), C.c_int32, C.c_int32, _f32p, C.c_void_p]),
+    "dr4sr_sasrec_encode_w_bwd": (C.c_int, [_PLANP, C.POINTER(SasrecInputs), C.c_int32, C.c_int32, _f32p, C.c_void_p]),
     "dr4sr_select_rows": (C.c_int, [_i64p, C.c_int64, _i64p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "dr4sr_embed_gather_posadd": (C.c_int, [_f32p, _f32p, _i64p, _f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "dr4sr_score_bce_fwd": (C.c_int, [_f32p, _f32p, _i64p, _i64p, _f32p, _f32p, _f32p, _f32p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
@@ -328,6 +335,11 @@ class Dr4srError(RuntimeError):
     pass
 
 
+# additive entry points of ABI 10 that a library named by DR4SR_LIB_PATH (the OTHER build of an A/B run, tools/lib_ab.sh) may predate; the
+# tree's own library must export them like every other symbol
+_AFTER_PARENT_AB = ("dr4sr_sasrec_encode_w", "dr4sr_sasrec_encode_w_bwd")
+
+
 def load():
     """dlopen the library once and type every entry point.  Raises if anything is missing."""
     global _lib
@@ -339,6 +351,8 @@ def load():
             "(or `make -C dr4sr_amd/csrc`).  dr4sr_amd has no CPU / PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SYMBOLS.items():
+        if name in _AFTER_PARENT_AB and os.environ.get("DR4SR_LIB_PATH") and not hasattr(lib, name):
+            continue                     # an older build under A/B: the call raises AttributeError where it is made
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -133,12 +133,13 @@ int launch_prep(const dr4sr_sasrec_plan* p, const Workspace& ws, int bump_rng, i
 // Packed forward, token-parallel: token t belongs to sequence slot b = find_seq(t) at pos = t - cu[b]:
 //   x[t,:] = drop(E[idx[row(b),pos],:] + P[pos,:])      (P == NULL: no position table, GRU4Rec)
 // One 16/32-lane group per token; the grid covers the worst case B*L tokens, groups beyond T exit.
-template <int D>
+// WGT (dr4sr_sasrec_inputs::input_weight, an instantiation of its own): x[t,:] = drop(inw[b,pos] * (E[..] + P[pos,:])) — the scale BEFORE the dropout
+template <int D, bool WGT = false>
 __global__ __launch_bounds__(256) void k_embed_fwd(const float* __restrict__ E, const float* __restrict__ P,
                                                    const int64_t* __restrict__ idx, const int64_t* __restrict__ rows,
                                                    const int* __restrict__ cu, float* __restrict__ X, int B, int L,
                                                    int n_items, const int* __restrict__ state, uint64_t seed, float p,
-                                                   int training) {
+                                                   int training, const float* __restrict__ inw) {
     constexpr int LPT = D / 4, TPB = 256 / LPT;
     const int T = state[DR4SR_STATE_T];
     const int t = blockIdx.x * TPB + threadIdx.x / LPT, c = (threadIdx.x % LPT) * 4;
@@ -152,6 +153,10 @@ __global__ __launch_bounds__(256) void k_embed_fwd(const float* __restrict__ E, 
         const float4 pe = ld4(P + (size_t)pos * D + c);
         o = make_float4(o.x + pe.x, o.y + pe.y, o.z + pe.z, o.w + pe.w);
     }
+    if constexpr (WGT) {
+        const float w = inw[(size_t)b * L + pos];
+        o.x *= w; o.y *= w; o.z *= w; o.w *= w;
+    }
     if (training && p > 0.f) {
         const RngKey rk = make_rng(seed, (uint32_t)state[DR4SR_STATE_RNGSTEP], p);
         const float4 m = drop4(rk, DR4SR_SITE_EMB, ((uint64_t)b * L + pos) * D + c);
@@ -161,26 +166,32 @@ __global__ __launch_bounds__(256) void k_embed_fwd(const float* __restrict__ E, 
 }
 
 int launch_embed_fwd_raw(const float* E, const float* P, const int64_t* idx, const int64_t* rows, const int* cu, float* X, int B,
-                         int L, int D, int n_items, const int* state, uint64_t seed, float p, int training, hipStream_t s) {
+                         int L, int D, int n_items, const int* state, uint64_t seed, float p, int training, hipStream_t s, const float* inw) {
     dim3 grid(((int64_t)B * L + (256 / (D / 4)) - 1) / (256 / (D / 4))), blk(256);
-    if (D == 64) hipLaunchKernelGGL(k_embed_fwd<64>, grid, blk, 0, s, E, P, idx, rows, cu, X, B, L, n_items, state, seed, p, training);
-    else hipLaunchKernelGGL(k_embed_fwd<128>, grid, blk, 0, s, E, P, idx, rows, cu, X, B, L, n_items, state, seed, p, training);
+#define EF(D_, W_) hipLaunchKernelGGL((k_embed_fwd<D_, W_>), grid, blk, 0, s, E, P, idx, rows, cu, X, B, L, n_items, state, seed, p, training, inw)
+    if (inw) { if (D == 64) EF(64, true); else EF(128, true); }
+    else if (D == 64) EF(64, false);
+    else EF(128, false);
+#undef EF
     return DR4SR_LAUNCH_CHECK();
 }
-int launch_embed_fwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s) {
+int launch_embed_fwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s, const float* inw) {
     return launch_embed_fwd_raw(p->params + ws.off[0], p->params + ws.off[1], p->in_item_id, p->rows, ws.cu, ws.X[0], p->B, p->L,
-                                p->D, p->n_items, p->state, p->seed, p->p_drop, training, s);
+                                p->D, p->n_items, p->state, p->seed, p->p_drop, training, s, inw);
 }
 
 // ------------------------------------------------------------------------------------------------
 // Packed backward, token-parallel: g = dX[t,:] * mask;  dE[idx,:] += g (skipped for idx == 0: padding_idx), dP[pos,:] += g.
 // Each block handles 64 consecutive tokens; dP is first accumulated in LDS (ds atomics) and flushed once per block.
-template <int D>
+// WGT (input_weight): d_inw[b,pos] = <g, E[clamped idx] + Pt[pos]> is STORED first (d_inw != NULL; one value per valid token, by the token's
+// first lane), then g <- inw[b,pos] * g in front of both accumulations.  E / Pt: the forward's tables.
+template <int D, bool WGT = false>
 __global__ __launch_bounds__(256) void k_embed_bwd(const float* __restrict__ dX, const int64_t* __restrict__ idx,
                                                    const int64_t* __restrict__ rows, const int* __restrict__ cu,
                                                    float* __restrict__ dE, float* __restrict__ dP, int B, int L,
                                                    int n_items, const int* __restrict__ state, uint64_t seed, float p,
-                                                   int training) {
+                                                   int training, const float* __restrict__ inw, float* __restrict__ d_inw,
+                                                   const float* __restrict__ E, const float* __restrict__ Pt) {
     constexpr int LPT = D / 4, TPB = 256 / LPT;
     __shared__ float accP[64 * D];                      // [L <= 64][D]
     const int T = state[DR4SR_STATE_T], t0 = blockIdx.x * 64;
@@ -197,6 +208,18 @@ __global__ __launch_bounds__(256) void k_embed_bwd(const float* __restrict__ dX,
         if (dodrop) {
             const float4 m = drop4(rk, DR4SR_SITE_EMB, ((uint64_t)b * L + pos) * D + c);
             g.x *= m.x; g.y *= m.y; g.z *= m.z; g.w *= m.w;
+        }
+        if constexpr (WGT) {
+            if (d_inw) {                                     // (uniform; the token's whole lane group is here: t is the group's)
+                int64_t ic = idx[row * L + pos];
+                ic = ic < 0 ? 0 : (ic >= n_items ? n_items - 1 : ic);      // the forward's clamp
+                float4 x = ld4(E + ic * D + c);
+                if (Pt) { const float4 pe = ld4(Pt + (size_t)pos * D + c); x = make_float4(x.x + pe.x, x.y + pe.y, x.z + pe.z, x.w + pe.w); }
+                const float sum = lane_group_sum<LPT>((g.x * x.x + g.y * x.y) + (g.z * x.z + g.w * x.w));
+                if (c == 0) d_inw[(size_t)b * L + pos] = sum;
+            }
+            const float w = inw[(size_t)b * L + pos];
+            g.x *= w; g.y *= w; g.z *= w; g.w *= w;
         }
         if (dP) {
             float* a = accP + pos * D + c;
@@ -218,15 +241,20 @@ __global__ __launch_bounds__(256) void k_embed_bwd(const float* __restrict__ dX,
 }
 
 int launch_embed_bwd_raw(const float* dX, const int64_t* idx, const int64_t* rows, const int* cu, float* dE, float* dP, int B, int L,
-                         int D, int n_items, const int* state, uint64_t seed, float p, int training, hipStream_t s) {
+                         int D, int n_items, const int* state, uint64_t seed, float p, int training, hipStream_t s,
+                         const float* inw, float* d_inw, const float* E, const float* P) {
     dim3 grid(((int64_t)B * L + 63) / 64), blk(256);
-    if (D == 64) hipLaunchKernelGGL(k_embed_bwd<64>, grid, blk, 0, s, dX, idx, rows, cu, dE, dP, B, L, n_items, state, seed, p, training);
-    else hipLaunchKernelGGL(k_embed_bwd<128>, grid, blk, 0, s, dX, idx, rows, cu, dE, dP, B, L, n_items, state, seed, p, training);
+    if (inw && !E) return DR4SR_E_ARG;
+#define EB(D_, W_) hipLaunchKernelGGL((k_embed_bwd<D_, W_>), grid, blk, 0, s, dX, idx, rows, cu, dE, dP, B, L, n_items, state, seed, p, training, inw, d_inw, E, P)
+    if (inw) { if (D == 64) EB(64, true); else EB(128, true); }
+    else if (D == 64) EB(64, false);
+    else EB(128, false);
+#undef EB
     return DR4SR_LAUNCH_CHECK();
 }
-int launch_embed_bwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s) {
+int launch_embed_bwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s, const float* inw, float* d_inw) {
     return launch_embed_bwd_raw(ws.dX[0], p->in_item_id, p->rows, ws.cu, p->grads + ws.off[0], p->grads + ws.off[1], p->B, p->L, p->D,
-                                p->n_items, p->state, p->seed, p->p_drop, training, s);
+                                p->n_items, p->state, p->seed, p->p_drop, training, s, inw, d_inw, p->params + ws.off[0], p->params + ws.off[1]);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -160,6 +160,8 @@ struct EmbQkvArgs {
     int xcd;                                   // 1: XCD-aware block -> tile order (xcd_tile below); the grid is a multiple of 8
     int wf_layers;                             // latency forms at d = 128: > 0 = this launch also writes the fragment-major fp32 weight images of that many layers to `sp` (wfrag_image_write)
     const unsigned short* sp;                  // at scale: layer 0's split-weight block (bf16x3 tile GEMMs), NULL: fp32 | latency forms, wf_layers > 0: the fp32 image buffer (as float*)
+    const float* inw;                          // input_weight [B][L] by batch slot (dr4sr_sasrec_inputs): x = drop(inw * (E[id] + P[pos])); read by the WGT instantiations only,
+                                               // which the launchers pick when it is not NULL — EVERY builder of this struct sets it
 };
 struct QkvEmbBwdArgs {
     const float* dQKV; const float* W; const float* dU1; const int64_t* idx; const int64_t* rows; const int* cu; const int* tile_seq;
@@ -167,6 +169,9 @@ struct QkvEmbBwdArgs {
     float* gout;                 // large batches: masked dx0 rows are stored here and scattered by a job of k_wgrad (overlaps its MFMA work)
     const float* kv_part; const int2* tok;     // deterministic latency form: layer 0's dK | dV partial blocks + the tokens' words (NULL: dQKV is complete)
     const unsigned short* sp;    // layer 0's split-weight block (bf16x3 tile GEMMs), NULL: fp32
+    // input_weight (dr4sr_sasrec_inputs; WGT instantiations only, picked when inw != NULL): with g = dx0 * mask, d_inw[b][pos] = <g, E[id] + P[pos]> is
+    // STORED (d_inw != NULL) and g <- inw[b][pos] * g before any consumer of g.  E / P: the forward's tables (set whenever inw is)
+    const float* inw; float* d_inw; const float* E; const float* P;
 };
 
 // scorer half of the fused last-layer launch (k_post_mid / k_wt_post_mid)
@@ -227,7 +232,7 @@ int launch_wt_post_fwd(const PostArgs& A, int Tmax, hipStream_t s);
 int launch_wt_post_bwd(const PostArgs& A, int Tmax, hipStream_t s);     // writes ln_part rows per 16-token tile
 
 int launch_wt_post_mid(const PostArgs& A, const ScoreTileArgs& S, int Tmax, hipStream_t s);
-int launch_wt_embqkv_fwd(const EmbQkvArgs& A, int Tmax, hipStream_t s);
+int launch_wt_embqkv_fwd(const EmbQkvArgs& A, int Tmax, hipStream_t s);                 // (A.inw != NULL, here and below: the weighted instantiations)
 int launch_wt_qkv_embed_bwd(const QkvEmbBwdArgs& A, int Tmax, hipStream_t s);          // gout form only (the scatter is a k_wgrad job)   // score_part / entries per 16-token tile
 
 int ffn_tile_rows(int Tmax);
@@ -246,8 +251,9 @@ int carve_workspace(const dr4sr_sasrec_plan* p, Workspace* ws);   // fills ws fr
 // adam_bc: k_prep also writes the bias-correction record of the optimizer step that follows it (the head of a dr4sr_sasrec_train_steps graph)
 int launch_prep(const dr4sr_sasrec_plan* p, const Workspace& ws, int bump_rng, int zero_grads, hipStream_t s, int adam_bc = 0);
 int make_prep_args(const dr4sr_sasrec_plan* p, const Workspace& ws, int bump_rng, PrepArgs* out);
-int launch_embed_fwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s);
-int launch_embed_bwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s);
+// inw / d_inw (here and in the layer-0 fusions below): dr4sr_sasrec_inputs' per-token input scale and its gradient, NULL = the unweighted launches
+int launch_embed_fwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s, const float* inw = nullptr);
+int launch_embed_bwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s, const float* inw = nullptr, float* d_inw = nullptr);
 int launch_unpack(const dr4sr_sasrec_plan* p, const Workspace& ws, const float* X, float* out, int mode, hipStream_t s);
 int launch_pack(const dr4sr_sasrec_plan* p, const Workspace& ws, const float* dout, float* dX, int mode, hipStream_t s);
 
@@ -259,8 +265,8 @@ int launch_wfrag_write(const dr4sr_sasrec_plan* p, const Workspace& ws, hipStrea
 bool wfrag_img_on(const dr4sr_sasrec_plan* p, const Workspace& ws);
 int launch_wsplit_raw(const float* params, unsigned short* img, int64_t o_in, int64_t o_out, int64_t o_w1, int64_t o_w2, int64_t layer_stride,
                       int E, int D, int F, int n_layer, hipStream_t s);       // ... from the images this launch writes (once per forward pass)
-int launch_embqkv_fwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s);
-int launch_qkv_embed_bwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s);
+int launch_embqkv_fwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s, const float* inw = nullptr);
+int launch_qkv_embed_bwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s, const float* inw = nullptr, float* d_inw = nullptr);
 int launch_post_mid(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s, const dr4sr_meta_weighting* mw = nullptr);
 int launch_qkv_fwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int layer, hipStream_t s);
 int launch_post_fwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int layer, int training, hipStream_t s);
@@ -270,7 +276,7 @@ int launch_qkv_bwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int layer, h
 // compute, so the fused step launches them early on a side stream (step.hip backward_layers); the table-gradient jobs (owner / scatter
 // planes), the embedding-stage plane and the scorer partials belong to the launch that holds layer 0
 int launch_wgrad(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, int with_score, hipStream_t s, bool qeb = false,
-                 bool meta = false, int l_lo = 0, int l_hi = -1, int table = -1);     // meta: the fused last-layer launch carried the MetaModel weighting (its tile size differs)
+                 bool meta = false, int l_lo = 0, int l_hi = -1, int table = -1, const float* inw = nullptr, float* d_inw = nullptr);     // meta: the fused last-layer launch carried the MetaModel weighting (its tile size differs)
 // table: -1 = the launch that holds layer 0 carries the item / position table jobs (owner planes, scatter plane); 1 = this launch carries
 // them whatever its layer range (which may be EMPTY: l_lo == l_hi), 0 = it does not — the two-bucket data-parallel step (step.hip)
 bool wgrad_table_jobs(const dr4sr_sasrec_plan* p, const Workspace& ws);      // the table gradient is a set of k_wgrad jobs (at scale, fused step)
@@ -304,9 +310,10 @@ int launch_prep_raw(const int64_t* seqlen, const int64_t* rows, int* cu, int* st
 int launch_prep_raw_hints(const int64_t* seqlen, const int64_t* rows, int* cu, int* state, int B, int L, int bump_rng, float* zero,
                           int64_t zero_floats, int* tile_seq, const PermSel& sel, hipStream_t s);
 int launch_embed_fwd_raw(const float* E, const float* P, const int64_t* idx, const int64_t* rows, const int* cu, float* X, int B,
-                         int L, int D, int n_items, const int* state, uint64_t seed, float p, int training, hipStream_t s);
+                         int L, int D, int n_items, const int* state, uint64_t seed, float p, int training, hipStream_t s, const float* inw = nullptr);
 int launch_embed_bwd_raw(const float* dX, const int64_t* idx, const int64_t* rows, const int* cu, float* dE, float* dP, int B, int L,
-                         int D, int n_items, const int* state, uint64_t seed, float p, int training, hipStream_t s);
+                         int D, int n_items, const int* state, uint64_t seed, float p, int training, hipStream_t s,
+                         const float* inw = nullptr, float* d_inw = nullptr, const float* E = nullptr, const float* P = nullptr);
 int launch_unpack_raw(const float* X, const int* cu, float* out, int B, int L, int D, int last, hipStream_t s);
 int launch_pack_raw(const float* dout, const int* cu, float* dX, int B, int L, int D, int last, hipStream_t s);
 int launch_score_packed_raw(const float* Z, const float* E, float* dE, float* dZ, const int64_t* target, const int64_t* rows,

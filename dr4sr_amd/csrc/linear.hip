@@ -273,7 +273,8 @@ int launch_wfrag_write(const dr4sr_sasrec_plan* p, const Workspace& ws, hipStrea
     return DR4SR_LAUNCH_CHECK();
 }
 
-template <int BM, int D>
+// WGT (A.inw, dr4sr_sasrec_inputs::input_weight; an instantiation of its own): x = drop(inw[b][pos] * (E[id] + P[pos])) — the scale BEFORE the dropout
+template <int BM, int D, bool WGT = false>
 __global__ __launch_bounds__(256) void k_embqkv_fwd(const EmbQkvArgs A) {
     constexpr int N = 3 * D, LDA = D + 4, LPT = D / 4, TPB = 256 / LPT;
     if constexpr (BM == 16 && D == 128) { if (A.wf_layers > 0) wfrag_image_write<D>(A); }      // every block, before the early exit of tile-less blocks
@@ -306,6 +307,10 @@ __global__ __launch_bounds__(256) void k_embqkv_fwd(const EmbQkvArgs A) {
                 o = ld4(A.E + id * D + c);
                 const float4 pe = ld4(A.P + (size_t)pos * D + c);
                 o = make_float4(o.x + pe.x, o.y + pe.y, o.z + pe.z, o.w + pe.w);
+                if constexpr (WGT) {
+                    const float w = A.inw[(size_t)b * A.L + pos];
+                    o.x *= w; o.y *= w; o.z *= w; o.w *= w;
+                }
                 if (dodrop) {
                     const float4 m = drop4(rk, DR4SR_SITE_EMB, ((uint64_t)b * A.L + pos) * D + c);
                     o.x *= m.x; o.y *= m.y; o.z *= m.z; o.w *= m.w;
@@ -324,7 +329,7 @@ __global__ __launch_bounds__(256) void k_embqkv_fwd(const EmbQkvArgs A) {
     if (A.dqkv_zero) zero_kv_rows<BM, D>(A.dqkv_zero, t0, T);
 }
 
-int launch_embqkv_fwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s) {
+int launch_embqkv_fwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s, const float* inw) {
     const int D = p->D, bm = tile_rows(ws);
     const size_t lds = sizeof(float) * bm * (D + 4);
     dim3 grid((ws.Tmax + bm - 1) / bm), blk(256);
@@ -333,14 +338,16 @@ int launch_embqkv_fwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int train
     A.W = p->params + poff(ws, 0, P_IN_W); A.bias = p->params + poff(ws, 0, P_IN_B); A.QKV = ws.layer[0].qkv; A.state = p->state;
     A.B = p->B; A.L = p->L; A.n_items = p->n_items; A.training = training; A.seed = p->seed; A.p = p->p_drop;
     A.idx32 = de_owner_mode(ws) ? ws.idx32 : nullptr;
-    A.sp = wsplit_of(p, ws, 0); A.wf_layers = 0;
+    A.sp = wsplit_of(p, ws, 0); A.wf_layers = 0; A.inw = inw;
     if (wfrag_img_on(p, ws)) { A.sp = reinterpret_cast<const unsigned short*>(ws.wfrag); A.wf_layers = p->n_layer; }
     const bool in_tile = attn_in_tile(p, ws);
     A.tok = (in_tile || ws.attn_tile_sa || attn_wave_on(p, ws)) ? ws.tok : nullptr; A.dqkv_zero = in_tile ? ws.layer[0].dqkv : nullptr;
     A.xcd = tile_xcd_order(p, ws) ? 1 : 0;
     if (A.xcd) grid.x = xcd_grid((int)grid.x, bm);
     if (wave_tiles(p, ws)) return launch_wt_embqkv_fwd(A, ws.Tmax, s);
-#define EQ(B_) do { if (D == 64) hipLaunchKernelGGL((k_embqkv_fwd<B_, 64>), grid, blk, lds, s, A); \
+#define EQ(B_) do { if (inw) { if (D == 64) hipLaunchKernelGGL((k_embqkv_fwd<B_, 64, true>), grid, blk, lds, s, A); \
+                                else hipLaunchKernelGGL((k_embqkv_fwd<B_, 128, true>), grid, blk, lds, s, A); } \
+                    else if (D == 64) hipLaunchKernelGGL((k_embqkv_fwd<B_, 64>), grid, blk, lds, s, A); \
                     else hipLaunchKernelGGL((k_embqkv_fwd<B_, 128>), grid, blk, lds, s, A); } while (0)
     BM_DISPATCH(bm, EQ);
 #undef EQ
@@ -1771,7 +1778,10 @@ int launch_qkv_bwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int layer, h
 // Layer-0 fusion of the backward tail: dx0 = dqkv W_in + du1 stays in LDS and is scattered straight into the tables
 // (a3 backward: g = dx0 * mask_emb; dE[idx] += g except padding_idx 0; dP[pos] += g), 16 lanes per token; dP is first
 // accumulated in LDS and flushed with one atomic per touched element per workgroup.
-template <int BM, int D, bool DET = false>
+// WGT (A.inw, input_weight; instantiations of their own): where g = dx0 * mask exists, d_inw[b][pos] = <g, E[id] + P[pos]> (the forward's clamped id)
+// is STORED first — one value per valid token, by the first lane of the token's lane group, when A.d_inw is set —, then g <- inw[b][pos] * g, and only
+// then come the consumers of g below (gout plane, LDS-merged dE atomics, dP): the tables pick the factor up with no change to their jobs.
+template <int BM, int D, bool DET = false, bool WGT = false>
 __device__ __forceinline__ void qkv_embed_bwd_body(const QkvEmbBwdArgs& A, const int t0, const int T) {
     constexpr int K = 3 * D, LDA = K + 4, LDC = D + 4, LPT = D / 4, TPB = 256 / LPT;
     float* As = smem;
@@ -1810,6 +1820,17 @@ __device__ __forceinline__ void qkv_embed_bwd_body(const QkvEmbBwdArgs& A, const
             if (dodrop) {
                 const float4 m = drop4(rk, DR4SR_SITE_EMB, ((uint64_t)b * A.L + pos) * D + c);
                 g.x *= m.x; g.y *= m.y; g.z *= m.z; g.w *= m.w;
+            }
+            if constexpr (WGT) {
+                if (A.d_inw) {                               // (uniform; the token's LPT lanes are all here: r and t are the lane group's)
+                    int64_t ic = A.idx[row * A.L + pos];
+                    ic = ic < 0 ? 0 : (ic >= A.n_items ? A.n_items - 1 : ic);
+                    const float4 e = ld4(A.E + ic * D + c), pe = ld4(A.P + (size_t)pos * D + c);
+                    const float sum = lane_group_sum<LPT>((g.x * (e.x + pe.x) + g.y * (e.y + pe.y)) + (g.z * (e.z + pe.z) + g.w * (e.w + pe.w)));
+                    if (c == 0) A.d_inw[(size_t)b * A.L + pos] = sum;
+                }
+                const float w = A.inw[(size_t)b * A.L + pos];
+                g.x *= w; g.y *= w; g.z *= w; g.w *= w;
             }
             if (A.gout) { st4(A.gout + (size_t)t * D + c, g); continue; }
             float* a = accP + pos * D + c;
@@ -1851,14 +1872,14 @@ __device__ __forceinline__ void qkv_embed_bwd_body(const QkvEmbBwdArgs& A, const
         if (v != 0.f) unsafeAtomicAdd(A.dP + i, v);
     }
 }
-template <int BM, int D, bool DET = false>
+template <int BM, int D, bool DET = false, bool WGT = false>
 __global__ __launch_bounds__(256) void k_qkv_embed_bwd(const QkvEmbBwdArgs A) {
     const int T = A.state[DR4SR_STATE_T], t0 = blockIdx.x * BM;
     if (t0 >= T) return;
-    qkv_embed_bwd_body<BM, D, DET>(A, t0, T);
+    qkv_embed_bwd_body<BM, D, DET, WGT>(A, t0, T);
 }
 
-static QkvEmbBwdArgs make_qeb_args(const dr4sr_sasrec_plan* p, const Workspace& ws, int training) {
+static QkvEmbBwdArgs make_qeb_args(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, const float* inw = nullptr, float* d_inw = nullptr) {
     const LayerWs& lw = ws.layer[0];
     QkvEmbBwdArgs A;
     A.dQKV = lw.dqkv; A.W = p->params + poff(ws, 0, P_IN_W); A.dU1 = lw.du1; A.idx = p->in_item_id; A.rows = p->rows; A.cu = ws.cu; A.tile_seq = ws.tile_seq;
@@ -1867,6 +1888,7 @@ static QkvEmbBwdArgs make_qeb_args(const dr4sr_sasrec_plan* p, const Workspace& 
     A.gout = scatter_in_wgrad(ws) ? ws.dX[0] : nullptr;
     A.kv_part = (ws.det_lat && ws.det_kv && attn_in_tile(p, ws)) ? ws.det_kv : nullptr; A.tok = ws.tok;
     A.sp = wsplit_of(p, ws, 0);
+    A.inw = inw; A.d_inw = inw ? d_inw : nullptr; A.E = p->params + ws.off[0]; A.P = p->params + ws.off[1];
     return A;
 }
 // latency regime: k_qkv_embed_bwd and k_wgrad are independent (the weight gradients read dqkv / X, not dx0), so the embedding tiles
@@ -1876,18 +1898,22 @@ bool qeb_in_wgrad(const Workspace& ws) {
     return !off && tile_rows(ws) == 16 && !ws.det_lat;       // (deterministic latency form: the embedding tiles complete layer 0's dqkv rows BEFORE k_wgrad reads them)
 }
 
-int launch_qkv_embed_bwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s) {
+int launch_qkv_embed_bwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s, const float* inw, float* d_inw) {
     const int D = p->D, bm = tile_rows(ws);
     const size_t lds = sizeof(float) * (bm * ((3 * D + 4) + (D + 4)) + (size_t)p->L * D + bm);
     dim3 grid((ws.Tmax + bm - 1) / bm), blk(256);
-    const QkvEmbBwdArgs A = make_qeb_args(p, ws, training);
+    const QkvEmbBwdArgs A = make_qeb_args(p, ws, training, inw, d_inw);
     if (wave_tiles(p, ws) && wt_bwd_on() && A.gout) return launch_wt_qkv_embed_bwd(A, ws.Tmax, s);
-#define QE(B_) do { if (B_ == 16 && A.kv_part) { if (D == 64) { big_lds((k_qkv_embed_bwd<16, 64, true>), lds); hipLaunchKernelGGL((k_qkv_embed_bwd<16, 64, true>), grid, blk, lds, s, A); } \
+#define QEW(B_, D_, DET_) do { big_lds((k_qkv_embed_bwd<B_, D_, DET_, true>), lds); hipLaunchKernelGGL((k_qkv_embed_bwd<B_, D_, DET_, true>), grid, blk, lds, s, A); } while (0)
+#define QE(B_) do { if (A.inw) { if (B_ == 16 && A.kv_part) { if (D == 64) QEW(16, 64, true); else QEW(16, 128, true); } \
+                                 else if (D == 64) QEW(B_, 64, false); else QEW(B_, 128, false); } \
+                    else if (B_ == 16 && A.kv_part) { if (D == 64) { big_lds((k_qkv_embed_bwd<16, 64, true>), lds); hipLaunchKernelGGL((k_qkv_embed_bwd<16, 64, true>), grid, blk, lds, s, A); } \
                                                  else { big_lds((k_qkv_embed_bwd<16, 128, true>), lds); hipLaunchKernelGGL((k_qkv_embed_bwd<16, 128, true>), grid, blk, lds, s, A); } } \
                     else if (D == 64) { big_lds(k_qkv_embed_bwd<B_, 64>, lds); hipLaunchKernelGGL((k_qkv_embed_bwd<B_, 64>), grid, blk, lds, s, A); } \
                     else { big_lds(k_qkv_embed_bwd<B_, 128>, lds); hipLaunchKernelGGL((k_qkv_embed_bwd<B_, 128>), grid, blk, lds, s, A); } } while (0)
     BM_DISPATCH(bm, QE);
 #undef QE
+#undef QEW
     return DR4SR_LAUNCH_CHECK();
 }
 
@@ -2368,14 +2394,15 @@ __device__ __forceinline__ void owner_job_sorted(const WgradArgs& A, const int o
 // four blocks spread that over four workgroups (measured in DESIGN.md section 5.00, round 4).
 // BLK with TB > 0 (what ships, TB = 2): [32 TB x 32] blocks whose four waves split the tokens (wgrad_ksplit_body); blockIdx.x is a token
 // chunk, not a tile.  TB = 0, the 64 x 64 blocks per 64-token tile of round 4, is a kernel of the experiments build (DR4SR_WGRAD_KSPLIT=0)
-template <int D, int F, bool BF, bool SUB = false, bool BLK = false, int TB = 0>
+// WGT: the embedding-stage plane carries an input_weight (qkv_embed_bwd_body<.., WGT>); nothing else of the launch differs
+template <int D, int F, bool BF, bool SUB = false, bool BLK = false, int TB = 0, bool WGT = false>
 __device__ __forceinline__ void wgrad_kernel_body(const WgradArgs& A, const QkvEmbBwdArgs& Q, const int noadd = 0) {
     // latency regime (A.qeb_plane): plane z = 0 of the grid is k_qkv_embed_bwd's work (16-row tiles, block-strided), layers shift by one
     const int layer = A.layer0 + (A.qeb_plane ? (int)blockIdx.z - 1 : (int)blockIdx.z);
     if (!SUB && layer < A.layer0) {
         const int T = A.state[DR4SR_STATE_T], nblk = gridDim.x * gridDim.y;
         for (int tile = blockIdx.y * gridDim.x + blockIdx.x; tile * 16 < T; tile += nblk) {
-            qkv_embed_bwd_body<16, D>(Q, tile * 16, T);
+            qkv_embed_bwd_body<16, D, false, WGT>(Q, tile * 16, T);
             __syncthreads();
         }
         return;
@@ -2436,16 +2463,16 @@ __device__ __forceinline__ void wgrad_kernel_body(const WgradArgs& A, const QkvE
         else wgrad_body<D, F>(J, A, part);
     }
 }
-template <int D, int F>
-__global__ __launch_bounds__(256) void k_wgrad(const WgradArgs A, const QkvEmbBwdArgs Q) { wgrad_kernel_body<D, F, false>(A, Q); }
+template <int D, int F, bool WGT = false>
+__global__ __launch_bounds__(256) void k_wgrad(const WgradArgs A, const QkvEmbBwdArgs Q) { wgrad_kernel_body<D, F, false, false, false, 0, WGT>(A, Q); }
 // the at-scale form with the weight-gradient GEMMs on the bf16 matrix cores (a separate kernel: its registers must not weigh on the fp32 one)
-template <int D, int F>
-__global__ __launch_bounds__(256) void k_wgrad_bf(const WgradArgs A, const QkvEmbBwdArgs Q) { wgrad_kernel_body<D, F, true>(A, Q); }
+template <int D, int F, bool WGT = false>
+__global__ __launch_bounds__(256) void k_wgrad_bf(const WgradArgs A, const QkvEmbBwdArgs Q) { wgrad_kernel_body<D, F, true, false, false, 0, WGT>(A, Q); }
 template <int D, int F>
 __global__ __launch_bounds__(256) void k_wgrad_bf64(const WgradArgs A, const QkvEmbBwdArgs Q) { wgrad_kernel_body<D, F, true, true>(A, Q); }
-template <int D, int F, int TB = 0>
+template <int D, int F, int TB = 0, bool WGT = false>
 __global__ __launch_bounds__(256) void k_wgrad_blk(const WgradArgs A, const QkvEmbBwdArgs Q, const int noadd) {
-    wgrad_kernel_body<D, F, false, false, true, TB>(A, Q, noadd);
+    wgrad_kernel_body<D, F, false, false, true, TB, WGT>(A, Q, noadd);
 }
 
 
@@ -2613,7 +2640,7 @@ static bool blk_env_on() { const char* e = DR4SR_XENV("DR4SR_WGRAD_BLK"); return
 bool wgrad_table_jobs(const dr4sr_sasrec_plan* p, const Workspace& ws) { (void)p; return scatter_in_wgrad(ws); }
 
 int launch_wgrad(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, int with_score, hipStream_t s, bool qeb, bool meta,
-                 int l_lo, int l_hi, int table) {
+                 int l_lo, int l_hi, int table, const float* inw, float* d_inw) {
     WgradArgs A;
     if (l_hi < 0) l_hi = p->n_layer;
     const bool tbl = table < 0 ? l_lo == 0 : table != 0;    // this launch carries the table jobs
@@ -2701,7 +2728,8 @@ int launch_wgrad(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, 
         A.sc_dE = G + ws.off[0]; A.sc_dP = G + ws.off[1]; A.sc_L = p->L; A.sc_n_items = p->n_items;
     }
     A.qeb_plane = (has0 && qeb && qeb_in_wgrad(ws)) ? 1 : 0;
-    const QkvEmbBwdArgs Q = make_qeb_args(p, ws, training);
+    const QkvEmbBwdArgs Q = make_qeb_args(p, ws, training, inw, d_inw);
+    const bool wq = A.qeb_plane && Q.inw;                   // the embedding-stage plane of THIS launch carries an input_weight: the WGT instantiations
     size_t lds = sub64 ? wgrad_lds_base(p) : sizeof(float) * 64 * (D + F > 2 * D ? D + F : 2 * D);
     if (scatter && sizeof(float) * p->L * D > lds) lds = sizeof(float) * p->L * D;
     // deterministic mode (Workspace::det): partial buffers instead of atomics + the ordered reduce launch below
@@ -2754,7 +2782,11 @@ int launch_wgrad(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, 
 #else
 #define WGX(D_, F_)
 #endif
-#define WG(D_, F_) do { WGX(D_, F_) if (blk64) WGB(D_, F_, 2); \
+#define WGW(K_) do { big_lds((K_), lds); hipLaunchKernelGGL((K_), grid, blk, lds, s, A, Q); } while (0)
+#define WG(D_, F_) do { if (wq) { if (blk64 && ks == 2) { big_lds((k_wgrad_blk<D_, F_, 2, true>), lds); hipLaunchKernelGGL((k_wgrad_blk<D_, F_, 2, true>), grid, blk, lds, s, A, Q, noadd); } \
+                                  else if (blk64 || sub64) return DR4SR_E_SHAPE;      /* (forms of the experiments build; k_wgrad_bf64 runs no embedding plane) */ \
+                                  else if (A.bf16x3) WGW((k_wgrad_bf<D_, F_, true>)); else WGW((k_wgrad<D_, F_, true>)); } \
+                        else WGX(D_, F_) if (blk64) WGB(D_, F_, 2); \
                         else if (sub64) { big_lds(k_wgrad_bf64<D_, F_>, lds); hipLaunchKernelGGL((k_wgrad_bf64<D_, F_>), grid, blk, lds, s, A, Q); } \
                         else if (A.bf16x3) { big_lds(k_wgrad_bf<D_, F_>, lds); hipLaunchKernelGGL((k_wgrad_bf<D_, F_>), grid, blk, lds, s, A, Q); } \
                         else { big_lds(k_wgrad<D_, F_>, lds); hipLaunchKernelGGL((k_wgrad<D_, F_>), grid, blk, lds, s, A, Q); } } while (0)
@@ -2763,6 +2795,7 @@ int launch_wgrad(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, 
     else if (D == 64 && F == 256) WG(64, 256);
     else return DR4SR_E_SHAPE;
 #undef WG
+#undef WGW
 #undef WGX
 #undef WGB
     if (A.det) {

@@ -852,7 +852,8 @@ __global__ __launch_bounds__(WT_WAVES * 64) void k_wt_post_mid(const PostArgs A,
 // ------------------------------------------------------------------------------------------------ layer-0 fusions, wave tiles
 // k_embqkv_fwd: x = drop(E[idx] + P[pos]) gathered straight into registers (a3: sasrec.py:42-48,:61-66), written once to X[0], and
 // multiplied by W_in in the same pass.  LDS: the in_proj image only (55 KB).
-template <int D, int WT_WAVES, bool EXACT = true>
+// WGT (A.inw, input_weight; an instantiation of its own): x = drop(inw[b][pos] * (E[idx] + P[pos]))
+template <int D, int WT_WAVES, bool EXACT = true, bool WGT = false>
 __global__ __launch_bounds__(WT_WAVES * 64) void k_wt_embqkv_fwd(const EmbQkvArgs A) {
     typedef WtImg<EXACT, 3 * D, D> In;
     constexpr int DT = D / 16, QT = 3 * D / 16;
@@ -883,6 +884,11 @@ __global__ __launch_bounds__(WT_WAVES * 64) void k_wt_embqkv_fwd(const EmbQkvArg
         wt_row_load<D>(pe, A.P + (size_t)pos * D, g);
 #pragma unroll
         for (int j = 0; j < DT; ++j) x[j] += pe[j];
+        if constexpr (WGT) {
+            const float wgt = A.inw[(size_t)b * A.L + pos];
+#pragma unroll
+            for (int j = 0; j < DT; ++j) x[j] *= wgt;
+        }
         if (dodrop) wt_row_drop<D>(x, rk, DR4SR_SITE_EMB, ((uint64_t)b * A.L + pos) * D, g);
         if (ok) wt_row_store<D>(A.X + (size_t)t * D, x, g);
         f32x4 q[QT];
@@ -898,7 +904,9 @@ __global__ __launch_bounds__(WT_WAVES * 64) void k_wt_embqkv_fwd(const EmbQkvArg
 }
 
 // k_qkv_embed_bwd (at-scale form): dx0 = dqkv W_in + du1, times the embedding-stage dropout mask, stored for k_wgrad's scatter / owner job
-template <int D, int WT_WAVES>
+// WGT (A.inw, input_weight; an instantiation of its own): d_inw[b][pos] = <gx, E[idx] + P[pos]> summed over the token's four lane groups (permlane
+// swaps) and stored by group 0 when A.d_inw is set, then gx <- inw[b][pos] * gx in front of the store
+template <int D, int WT_WAVES, bool WGT = false>
 __global__ __launch_bounds__(WT_WAVES * 64) void k_wt_qkv_embed_bwd(const QkvEmbBwdArgs A) {
     typedef WtImg<true, 3 * D, D> In;
     constexpr int DT = D / 16, QT = 3 * D / 16;
@@ -923,6 +931,28 @@ __global__ __launch_bounds__(WT_WAVES * 64) void k_wt_qkv_embed_bwd(const QkvEmb
         if (dodrop) {
             const int b = find_seq_from(A.cu, A.B, tt, A.tile_seq[tile]), pos = tt - A.cu[b];
             wt_row_drop<D>(gx, rk, DR4SR_SITE_EMB, ((uint64_t)b * A.L + pos) * D, g);
+        }
+        if constexpr (WGT) {                                // (rows past T repeat token T - 1 and store nothing: every lane takes part in the swaps)
+            const int b = find_seq_from(A.cu, A.B, tt, A.tile_seq[tile]), pos = tt - A.cu[b];
+            if (A.d_inw) {
+                const int64_t row = A.rows ? A.rows[b] : b;
+                int64_t id = A.idx[row * A.L + pos];
+                id = id < 0 ? 0 : (id >= A.n_items ? A.n_items - 1 : id);
+                f32x4 e[DT], pe[DT];
+                wt_row_load<D>(e, A.E + (size_t)id * D, g);
+                wt_row_load<D>(pe, A.P + (size_t)pos * D, g);
+                float sum = 0.f;
+#pragma unroll
+                for (int j = 0; j < DT; ++j) {
+                    e[j] += pe[j];
+                    sum += (gx[j][0] * e[j][0] + gx[j][1] * e[j][1]) + (gx[j][2] * e[j][2] + gx[j][3] * e[j][3]);
+                }
+                sum = xrow_sum(sum);
+                if (ok && g == 0) A.d_inw[(size_t)b * A.L + pos] = sum;
+            }
+            const float wgt = A.inw[(size_t)b * A.L + pos];
+#pragma unroll
+            for (int j = 0; j < DT; ++j) gx[j] *= wgt;
         }
         if (ok) wt_row_store<D>(A.gout + (size_t)t * D, gx, g);
     }
@@ -976,8 +1006,14 @@ template <int W>
 int wt_embqkv_launch(const EmbQkvArgs& A, int grid, hipStream_t s) {
     const size_t lds = WtImg<true, 192, 64>::bytes + 4 * 192;
     if (DR4SR_XENV("DR4SR_WT_EMB_BF16X3")) {                 // the in_proj GEMM as a bf16x3 split (same image bytes)
+        if (A.inw) return DR4SR_E_SHAPE;                     // (no weighted instantiation of the experiment)
         big_lds(k_wt_embqkv_fwd<64, W, false>, lds);
         hipLaunchKernelGGL((k_wt_embqkv_fwd<64, W, false>), dim3(grid), dim3(W * 64), lds, s, A);
+        return DR4SR_LAUNCH_CHECK();
+    }
+    if (A.inw) {
+        big_lds((k_wt_embqkv_fwd<64, W, true, true>), lds);
+        hipLaunchKernelGGL((k_wt_embqkv_fwd<64, W, true, true>), dim3(grid), dim3(W * 64), lds, s, A);
         return DR4SR_LAUNCH_CHECK();
     }
     big_lds(k_wt_embqkv_fwd<64, W>, lds);
@@ -987,6 +1023,11 @@ int wt_embqkv_launch(const EmbQkvArgs& A, int grid, hipStream_t s) {
 template <int W>
 int wt_qeb_launch(const QkvEmbBwdArgs& A, int grid, hipStream_t s) {
     const size_t lds = WtImg<true, 192, 64>::bytes;
+    if (A.inw) {
+        big_lds((k_wt_qkv_embed_bwd<64, W, true>), lds);
+        hipLaunchKernelGGL((k_wt_qkv_embed_bwd<64, W, true>), dim3(grid), dim3(W * 64), lds, s, A);
+        return DR4SR_LAUNCH_CHECK();
+    }
     big_lds(k_wt_qkv_embed_bwd<64, W>, lds);
     hipLaunchKernelGGL((k_wt_qkv_embed_bwd<64, W>), dim3(grid), dim3(W * 64), lds, s, A);
     return DR4SR_LAUNCH_CHECK();

@@ -533,11 +533,13 @@ static int attn_bwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int l, int 
 }
 
 // mid_fused: the last layer's post_fwd / scorer / post_bwd run as ONE launch (launch_post_mid) between the two halves
-static int forward_layers(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s, bool mid_fused = false) {
+// inw: dr4sr_sasrec_inputs::input_weight — the embedding-stage launch of whatever form the plan has takes it; nothing behind X[0] changes
+static int forward_layers(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, hipStream_t s, bool mid_fused = false,
+                          const float* inw = nullptr) {
     const bool fuse = DR4SR_ENV("DR4SR_NO_FUSE") == nullptr;     // qkv of layer l>0 is emitted by post_fwd(l-1),
     if (tile_bf3(p, ws)) RC(launch_wsplit(p, ws, s));                // d = 128 at scale: this pass's weights as bf16 hi | lo images
-    if (fuse) RC(launch_embqkv_fwd(p, ws, training, s));             // qkv of layer 0 by the embedding gather
-    else { RC(launch_embed_fwd(p, ws, training, s)); if (wfrag_img_on(p, ws)) RC(launch_wfrag_write(p, ws, s)); }
+    if (fuse) RC(launch_embqkv_fwd(p, ws, training, s, inw));        // qkv of layer 0 by the embedding gather
+    else { RC(launch_embed_fwd(p, ws, training, s, inw)); if (wfrag_img_on(p, ws)) RC(launch_wfrag_write(p, ws, s)); }
     const bool in_tile = attn_in_tile(p, ws);                    // the attention runs at the head of post_fwd / post_mid (attn_tile.h)
     for (int l = 0; l < p->n_layer; ++l) {
         if (!fuse) RC(launch_qkv_fwd(p, ws, l, s));
@@ -565,7 +567,7 @@ static bool dp_two_buckets(const dr4sr_sasrec_plan* p, const Workspace& ws) {
 
 // phase 0: the whole backward; 1: up to and including the launch that completes the table bucket; 2: what is left (one launch)
 static int backward_layers(const dr4sr_sasrec_plan* p, const Workspace& ws, int training, int with_score, hipStream_t s,
-                           bool mid_fused = false, bool meta = false, int phase = 0) {
+                           bool mid_fused = false, bool meta = false, int phase = 0, const float* inw = nullptr, float* d_inw = nullptr) {
     const bool fused = !DR4SR_ENV("DR4SR_NO_FUSE");
     const bool two = phase != 0 && dp_two_buckets(p, ws);
     if (phase == 2) return two ? launch_wgrad(p, ws, training, with_score, s, fused, meta, 0, dp_split_layer(p), 0) : 0;
@@ -587,11 +589,12 @@ static int backward_layers(const dr4sr_sasrec_plan* p, const Workspace& ws, int 
             forked = true;
         }
     }
-    if (!fused) RC(launch_embed_bwd(p, ws, training, s));
-    else if (!qeb_in_wgrad(ws)) RC(launch_qkv_embed_bwd(p, ws, training, s));
+    // (input_weight: the embedding-stage backward is one of these two launches or, qeb_in_wgrad, the first plane of the LAST k_wgrad launch below)
+    if (!fused) RC(launch_embed_bwd(p, ws, training, s, inw, d_inw));
+    else if (!qeb_in_wgrad(ws)) RC(launch_qkv_embed_bwd(p, ws, training, s, inw, d_inw));
     if (forked) RC(fk.join(s, 2, 1));
     if (two) return launch_wgrad(p, ws, training, with_score, s, fused, meta, dp_split_layer(p), p->n_layer, 1);
-    RC(launch_wgrad(p, ws, training, with_score, s, fused, meta, 0, forked ? 1 : -1));
+    RC(launch_wgrad(p, ws, training, with_score, s, fused, meta, 0, forked ? 1 : -1, -1, inw, d_inw));
     return 0;
 }
 
@@ -711,25 +714,37 @@ extern "C" int dr4sr_sasrec_train_steps(const dr4sr_sasrec_plan* plan, int32_t n
     return 0;
 }
 
-extern "C" int dr4sr_sasrec_encode(const dr4sr_sasrec_plan* plan, int32_t training, int32_t pooling, float* out,
-                                   void* stream) {
+// in == NULL or in->input_weight == NULL: the unweighted launches (dr4sr_sasrec_encode / _encode_bwd ARE these calls with in = NULL)
+extern "C" int dr4sr_sasrec_encode_w(const dr4sr_sasrec_plan* plan, const dr4sr_sasrec_inputs* in, int32_t training, int32_t pooling, float* out,
+                                     void* stream) {
     Workspace ws;
     RC(get_ws(plan, &ws));
     if (!out || pooling < DR4SR_POOL_NONE || pooling > DR4SR_POOL_MEAN) return DR4SR_E_ARG;
+    if (in && in->d_input_weight && !in->input_weight) return DR4SR_E_ARG;
     hipStream_t s = (hipStream_t)stream;
     RC(launch_prep(plan, ws, training ? 1 : 0, 0, s));
-    RC(forward_layers(plan, ws, training, s));
+    RC(forward_layers(plan, ws, training, s, false, in ? in->input_weight : nullptr));
     return launch_unpack(plan, ws, ws.X[plan->n_layer], out, pooling == DR4SR_POOL_LAST ? 1 : pooling == DR4SR_POOL_MEAN ? 2 : 0, s);
 }
 
-extern "C" int dr4sr_sasrec_encode_bwd(const dr4sr_sasrec_plan* plan, int32_t training, int32_t pooling,
-                                       const float* d_out, void* stream) {
+extern "C" int dr4sr_sasrec_encode(const dr4sr_sasrec_plan* plan, int32_t training, int32_t pooling, float* out,
+                                   void* stream) {
+    return dr4sr_sasrec_encode_w(plan, nullptr, training, pooling, out, stream);
+}
+
+extern "C" int dr4sr_sasrec_encode_w_bwd(const dr4sr_sasrec_plan* plan, const dr4sr_sasrec_inputs* in, int32_t training, int32_t pooling,
+                                         const float* d_out, void* stream) {
     Workspace ws;
     RC(get_ws(plan, &ws));
     if (!d_out || !plan->grads || pooling < DR4SR_POOL_NONE || pooling > DR4SR_POOL_MEAN) return DR4SR_E_ARG;
+    if (in && in->d_input_weight && !in->input_weight) return DR4SR_E_ARG;
     hipStream_t s = (hipStream_t)stream;
     RC(launch_pack(plan, ws, d_out, ws.dX[plan->n_layer], pooling == DR4SR_POOL_LAST ? 1 : pooling == DR4SR_POOL_MEAN ? 2 : 0, s));
-    return backward_layers(plan, ws, training, 0, s);
+    return backward_layers(plan, ws, training, 0, s, false, false, 0, in ? in->input_weight : nullptr, in ? in->d_input_weight : nullptr);
+}
+extern "C" int dr4sr_sasrec_encode_bwd(const dr4sr_sasrec_plan* plan, int32_t training, int32_t pooling,
+                                       const float* d_out, void* stream) {
+    return dr4sr_sasrec_encode_w_bwd(plan, nullptr, training, pooling, d_out, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -122,6 +122,40 @@ class SasrecEngine(FlatEngine):
         return p
 
     # ------------------------------------------------------------------------------------------
+    # KEPT DIFFERENCE: only SASRec's encoder takes a per-token input scale (include/dr4sr_hip.h: dr4sr_sasrec_inputs)
+    def _check_weight(self, plan, t, what):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (plan.B, self.L) or t.device != self.params.device:
+            raise _lib.Dr4srError(f"SASRec: {what} must be a contiguous fp32 [{plan.B}, {self.L}] tensor on {self.params.device}, got "
+                                  f"{t.dtype} {tuple(t.shape)} on {t.device}")
+
+    def encode(self, plan, training: bool, pooling: int, out=None, input_weight=None):
+        """input_weight [B, L] (by batch slot): x = dropout(input_weight * (E[id] + P[pos])), sasrec.py:61-64; None = the unweighted call"""
+        if input_weight is None:
+            return FlatEngine.encode(self, plan, training, pooling, out)
+        self._check_weight(plan, input_weight, "input_weight")
+        if out is None:
+            shape = (plan.B, self.D) if pooling in self.POOLED else (plan.B, self.L, self.D)
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        ins = _lib.SasrecInputs(_lib.ptr(input_weight), None)
+        _lib.check(self.lib.dr4sr_sasrec_encode_w(C.byref(plan), C.byref(ins), int(training), pooling, _lib.ptr(out), _lib.cur_stream()),
+                   "dr4sr_sasrec_encode_w")
+        return out
+
+    def encode_bwd(self, plan, training: bool, pooling: int, d_out: torch.Tensor, input_weight=None, d_input_weight=None):
+        """input_weight: the forward's; d_input_weight [B, L]: receives the weight's gradient — written for pos < seqlen, so the caller
+        hands a zero-filled buffer (the other positions' gradient is 0)"""
+        if input_weight is None and d_input_weight is None:
+            return FlatEngine.encode_bwd(self, plan, training, pooling, d_out)
+        if input_weight is not None:
+            self._check_weight(plan, input_weight, "input_weight")
+        if d_input_weight is not None:
+            self._check_weight(plan, d_input_weight, "d_input_weight")
+        ins = _lib.SasrecInputs(_lib.ptr(input_weight) if input_weight is not None else None,
+                                _lib.ptr(d_input_weight) if d_input_weight is not None else None)
+        _lib.check(self.lib.dr4sr_sasrec_encode_w_bwd(C.byref(plan), C.byref(ins), int(training), pooling, _lib.ptr(d_out.contiguous()),
+                                                      _lib.cur_stream()), "dr4sr_sasrec_encode_w_bwd")
+
+    # ------------------------------------------------------------------------------------------
     # KEPT DIFFERENCE: the data-parallel step in pieces (parallel.py) exists for SASRec only
     def fwd_bwd_prepared(self, plan):
         self._call("dr4sr_sasrec_fwd_bwd_prepared", plan)

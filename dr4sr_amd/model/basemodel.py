@@ -108,22 +108,32 @@ class _ScoreBCE(torch.autograd.Function):
 
 class _Encode(torch.autograd.Function):
     """a model's query encoder through engine.encode / engine.encode_bwd.  plan_args, plan_kw: what engine.make_plan takes besides the
-    ids ((seqlen,) where the model has lengths; SASRec's slot); enc_args: what encode takes besides the plan and the mode ((pooling,))"""
+    ids ((seqlen,) where the model has lengths; SASRec's slot); enc_args: what encode takes besides the plan and the mode ((pooling,)).
+    weight (SASRec only, an eighth argument): the batch's input_weight as a contiguous fp32 [B, L] tensor (model/sasrec.py expands and casts it
+    with torch ops OUTSIDE, so autograd reduces the gradient to the caller's shape); its gradient is asked of the engine when it requires one"""
 
     @staticmethod
-    def forward(ctx, model, anchor, idx, plan_args, plan_kw, training, enc_args):
+    def forward(ctx, model, anchor, idx, plan_args, plan_kw, training, enc_args, weight=None):
         eng = model.engine
         idx, plan_args = idx.contiguous(), tuple(t.contiguous() for t in plan_args)
-        out = eng.encode(eng.make_plan(idx, None, *plan_args, **plan_kw), training, *enc_args)
+        kw = {} if weight is None else {"input_weight": weight.detach()}
+        out = eng.encode(eng.make_plan(idx, None, *plan_args, **plan_kw), training, *enc_args, **kw)
         ctx.model, ctx.args = model, (idx, plan_args, plan_kw, training, enc_args)
+        if weight is not None:
+            ctx.save_for_backward(weight)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         idx, plan_args, plan_kw, training, enc_args = ctx.args
         eng = ctx.model.engine
-        eng.encode_bwd(eng.make_plan(idx, None, *plan_args, **plan_kw), training, *enc_args, gout.contiguous())
-        return None, None, None, None, None, None, None
+        if not ctx.saved_tensors:
+            eng.encode_bwd(eng.make_plan(idx, None, *plan_args, **plan_kw), training, *enc_args, gout.contiguous())
+            return None, None, None, None, None, None, None
+        w = ctx.saved_tensors[0].detach()
+        dw = torch.zeros_like(w) if ctx.needs_input_grad[7] else None      # written for pos < seqlen only: the rest stays 0
+        eng.encode_bwd(eng.make_plan(idx, None, *plan_args, **plan_kw), training, *enc_args, gout.contiguous(), input_weight=w, d_input_weight=dw)
+        return None, None, None, None, None, None, None, dw
 
 
 class BaseModel(nn.Module):

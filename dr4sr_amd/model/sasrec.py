@@ -103,8 +103,9 @@ class SASRecQueryEncoder(nn.Module):
     def forward(self, batch, need_pooling=True, slot=0, pooling=None):
         """slot: engine workspace of this pass (passes whose backward has not run yet must not share one); pooling: override
         ('mean' = module/functional.py:50-55 fused into the encoder call, used by the CL4SRec views)"""
-        if batch.get("seq_emb", None) is not None or "input_weight" in batch:
-            raise NotImplementedError("seq_emb / input_weight inputs are unused by the shipped configs and not on the HIP path")
+        if batch.get("seq_emb", None) is not None:
+            raise NotImplementedError("seq_emb input (an encoder input without item ids) is unused by the shipped configs and not on the HIP path")
+        weight = self._input_weight(batch)
         if pooling is not None:
             pooling = self._POOL[pooling]
         elif not need_pooling:
@@ -112,8 +113,31 @@ class SASRecQueryEncoder(nn.Module):
         else:
             pooling = self._POOL[self.training_pooling_type if self.training else self.eval_pooling_type]
         model = self._owner[0]
-        return _Encode.apply(model, model.item_embedding.weight, batch["in_" + self.fiid], (batch["seqlen"],), {"slot": slot},
-                             bool(self.training), (pooling,))
+        args = (model, model.item_embedding.weight, batch["in_" + self.fiid], (batch["seqlen"],), {"slot": slot}, bool(self.training), (pooling,))
+        return _Encode.apply(*args) if weight is None else _Encode.apply(*args, weight)
+
+    def _input_weight(self, batch):
+        """batch['input_weight'] (sasrec.py:61-64: `input_weight * (seq_embs + position_embs)`; an absent key or None = no weight, as the
+        reference's bare except makes it) as the contiguous fp32 [B, L] the engine takes.  Supported: every shape that broadcasts to
+        [B, L, 1] — [B, L, 1], [1, L, 1], [B, 1, 1], [L, 1], [1], a scalar.  The expansion and the cast are torch ops, so autograd's own
+        expand / cast backward hands the gradient back in the caller's shape and dtype."""
+        w = batch.get("input_weight", None)
+        if w is None:
+            return None
+        ids = batch["in_" + self.fiid]
+        B, L = int(ids.shape[0]), int(ids.shape[1])
+        w = torch.as_tensor(w, device=ids.device)
+        ok = w.dim() == 0 or (w.dim() <= 3 and w.shape[-1] == 1)
+        if ok:
+            try:
+                ok = tuple(torch.broadcast_shapes(tuple(w.shape), (B, L, 1))) == (B, L, 1)
+            except RuntimeError:
+                ok = False
+        if not ok:
+            raise NotImplementedError(f"HIP SASRec: input_weight must broadcast to [B, L, 1] = [{B}, {L}, 1] (one scale per position: [B, L, 1], "
+                                      f"[1, L, 1], [B, 1, 1], [L, 1] or a scalar), got {tuple(w.shape)}; a weight with a feature dimension is not "
+                                      "on the HIP path")
+        return w.to(torch.float32).expand(B, L, 1).reshape(B, L).contiguous()
 
 
 class SASRec(FlatEngineModel):

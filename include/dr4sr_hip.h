@@ -4,7 +4,8 @@
  * boundary a maintainer would bind is therefore "what the reference asks torch to do" on
  *   model/basemodel.py:177-214  (training_epoch / training_step: neg-sampling, encoder forward,
  *                                tied-embedding scorer, BCE, backward, Adam)
- *   model/sasrec.py:39-75       (SASRecQueryEncoder.forward)
+ *   model/sasrec.py:39-75       (SASRecQueryEncoder.forward; its batch['input_weight'] scale: dr4sr_sasrec_inputs,
+ *                                dr4sr_sasrec_encode_w / _encode_w_bwd — seq_emb is not bound)
  *   model/loss_func.py:9-38     (BinaryCrossEntropyLoss)
  *   model/basemodel.py:354-365  (topk: full-item scorer)
  * Every entry point below names the reference lines it replaces.  INTEGRATION.md shows the
@@ -251,6 +252,28 @@ int dr4sr_sasrec_encode(const dr4sr_sasrec_plan* plan, int32_t training, int32_t
  * into plan->grads (exactly d_out-weighted, no normalisation). */
 int dr4sr_sasrec_encode_bwd(const dr4sr_sasrec_plan* plan, int32_t training, int32_t pooling,
                             const float* d_out, void* stream);
+
+/* The encoder's optional inputs (sasrec.py:61-64: `batch['input_weight'] * (seq_embs + position_embs)` when the batch carries a weight).
+ * Additive to ABI 10: the plan struct is untouched.
+ *   input_weight: one scale per position, x = dropout(input_weight[b,pos] * (E[id] + P[pos])) — the scale sits BEFORE the embedding-stage
+ *     dropout, as in the reference; everything behind the encoder's input is unchanged.  Indexed by the BATCH SLOT b of the plan, not
+ *     through plan->rows (it belongs to the batch, not to the dataset).  Values at pos >= seqlen[b] are never read.
+ *   d_input_weight (backward only): d_input_weight[b,pos] = sum_c g[b,pos,c] * (E[id] + P[pos])[c] with g the gradient that reaches the
+ *     dropout's input.  WRITTEN, not accumulated (a second backward on one forward stores the same values), for pos < seqlen[b] only:
+ *     the caller zero-fills the buffer, the reference's gradient is 0 at the other positions for every pooling of this library.
+ *     The item / position table gradients pick the factor input_weight[b,pos] up.
+ * in == NULL or in->input_weight == NULL is dr4sr_sasrec_encode / _encode_bwd: the same launches, the same bits (those two ARE these calls
+ * with in = NULL).  d_input_weight without input_weight: DR4SR_E_ARG.  The backward takes the input_weight of the forward it differentiates.
+ * The fused training steps (dr4sr_sasrec_fwd_bwd, _train_step(s), _weighted) take their rows from dataset tensors and stay unweighted;
+ * seq_emb (an encoder input without item ids) is not on this path. */
+typedef struct dr4sr_sasrec_inputs {
+    const float* input_weight;    /* [B,L] fp32 by BATCH SLOT b (not through plan->rows), or NULL */
+    float*       d_input_weight;  /* [B,L] or NULL; backward only; written, zero-filled by the caller */
+} dr4sr_sasrec_inputs;
+int dr4sr_sasrec_encode_w(const dr4sr_sasrec_plan* plan, const dr4sr_sasrec_inputs* in, int32_t training, int32_t pooling,
+                          float* out, void* stream);
+int dr4sr_sasrec_encode_w_bwd(const dr4sr_sasrec_plan* plan, const dr4sr_sasrec_inputs* in, int32_t training, int32_t pooling,
+                              const float* d_out, void* stream);
 
 /* a1: device-side batch selection replacing DataLoader(shuffle=True) + per-sample __getitem__ +
  * default_collate (data/dataset.py:105-108, :149-164).  rows_out[i] = perm[(c*stride + offset + i)
