@@ -286,6 +286,10 @@ SYMBOLS = {
     "dr4sr_pairs_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
     "dr4sr_pairs_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, _i64p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64,
                                     C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # additive to ABI 10: pattern mining for the regenerator (csrc/mine.hip)
+    "dr4sr_mine_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int64]),
+    "dr4sr_mine_patterns": (C.c_int, [C.c_void_p, _i64p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int64,
+                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, _i64p, C.c_void_p]),
     # additive to ABI 10: teacher-forced scoring of the regenerator (csrc/regen_score.hip)
     "dr4sr_regen_score_param_layout": (C.c_int64, [C.c_int32, C.c_int32, C.c_void_p]),
     "dr4sr_regen_score_workspace_bytes": (C.c_int64, [_RPLANP, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
@@ -337,7 +341,7 @@ class Dr4srError(RuntimeError):
 
 # additive entry points of ABI 10 that a library named by DR4SR_LIB_PATH (the OTHER build of an A/B run, tools/lib_ab.sh) may predate; the
 # tree's own library must export them like every other symbol
-_AFTER_PARENT_AB = ("dr4sr_sasrec_encode_w", "dr4sr_sasrec_encode_w_bwd")
+_AFTER_PARENT_AB = ("dr4sr_sasrec_encode_w", "dr4sr_sasrec_encode_w_bwd", "dr4sr_mine_workspace_bytes", "dr4sr_mine_patterns")
 
 
 def load():

@@ -16,7 +16,8 @@ Python's unseeded `random`, so its file is not reproducible bit for bit by anyth
 
 backend="hip" is the kernel; backend="numpy" restates it on the host with integer numpy (same subsequence rule, same signatures, same
 Philox keys), so both return identical arrays and the module works without a GPU.  Nothing switches backends on its own.
-Mining itself stays with seq2pat (`sequential.seq2pat`): pass what `Seq2Pat.get_patterns` returned, or let the CLI import it.
+Mining: pass what `Seq2Pat.get_patterns` returned, let the CLI import seq2pat (`sequential.seq2pat`, the default), or mine with this
+project's own miner (dr4sr_amd/mine.py: `miner="hip"` / `"numpy"`, `--miner hip|numpy`), which needs no seq2pat.
 """
 from __future__ import annotations
 
@@ -258,14 +259,30 @@ def mine_patterns(root_path: str, alpha: int = 5, beta: int = 2, n_jobs: int = 2
     return Seq2Pat(sequences=data, n_jobs=n_jobs, max_span=alpha).get_patterns(min_frequency=beta)
 
 
+MINERS = ("seq2pat", "hip", "numpy")
+
+
+def _mine(root_path, alpha, beta, n_jobs, miner, device):
+    """seq2pat_data.pth under root_path -> the mined list: with seq2pat itself (the default), or with this project's miner
+    (dr4sr_amd/mine.py, its HIP or its numpy backend), which never imports `sequential`"""
+    miner = "seq2pat" if miner is None else miner
+    if miner not in MINERS:
+        raise ValueError(f"miner must be one of {MINERS}, not {miner!r}")
+    if miner == "seq2pat":
+        return mine_patterns(root_path, alpha, beta, n_jobs)
+    from .mine import mine_file
+    return mine_file(root_path, alpha, beta, miner, device)
+
+
 def build_pretraining_dataset(root_path: str, patterns=None, alpha: int = 5, beta: int = 2, n_jobs: int = 2, seed: int = 0,
-                              backend: str = "hip", device="cuda"):
+                              backend: str = "hip", device="cuda", miner: str | None = None):
     """1.Build_pretraining_dataset.py's __main__: reads train.pth under root_path, writes patterns.pth (pattern rows + training rows)
     and seq-pat-pair.pth next to it; returns both paths.  `patterns`: what Seq2Pat.get_patterns returned (each pattern's ids followed
-    by its frequency); None mines them as the reference does (alpha = max_span, beta = min_frequency)."""
+    by its frequency); None mines them from seq2pat_data.pth (alpha = max_span, beta = min_frequency) with `miner`: None / "seq2pat" as
+    the reference does, "hip" / "numpy" with dr4sr_amd.mine."""
     import torch
     if patterns is None:
-        patterns = mine_patterns(root_path, alpha, beta, n_jobs)
+        patterns = _mine(root_path, alpha, beta, n_jobs, miner, device)
     values = [[int(v) for v in p] for p in pattern_values(patterns)]
     train = torch.load(os.path.join(root_path, "train.pth"))
     pat_path = os.path.join(root_path, "patterns.pth")
@@ -288,20 +305,25 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="seed of the random choice of ten patterns per sequence")
     ap.add_argument("--backend", type=str, default="hip", choices=("hip", "numpy"))
     ap.add_argument("--gpu", type=int, default=0)
+    ap.add_argument("--miner", type=str, default="seq2pat", choices=MINERS,
+                    help="who mines seq2pat_data.pth without --patterns_file: seq2pat (the `sequential` package), or dr4sr_amd.mine on the "
+                         "GPU (hip) or the host (numpy)")
     a = ap.parse_args(argv)
     import torch
+    device = "cpu"
+    if "hip" in (a.backend, a.miner if a.patterns_file is None else None):
+        torch.cuda.set_device(a.gpu)
+        device = torch.device("cuda", a.gpu)
     if a.patterns_file is not None:
         patterns = torch.load(a.patterns_file)
     else:
         try:
-            patterns = mine_patterns(a.root_path, a.alpha, a.beta, a.n_jobs)
+            patterns = _mine(a.root_path, a.alpha, a.beta, a.n_jobs, a.miner, device)
         except ImportError as e:
+            if a.miner != "seq2pat":
+                raise
             sys.exit(f"dr4sr_amd.pairs: cannot import sequential.seq2pat ({e}); mine the patterns where seq2pat is installed, "
-                     f"torch.save what Seq2Pat.get_patterns returned, and pass it with --patterns_file")
-    device = "cpu"
-    if a.backend == "hip":
-        torch.cuda.set_device(a.gpu)
-        device = torch.device("cuda", a.gpu)
+                     f"torch.save what Seq2Pat.get_patterns returned, and pass it with --patterns_file (or mine here with --miner hip)")
     for path in build_pretraining_dataset(a.root_path, patterns, a.alpha, a.beta, a.n_jobs, a.seed, a.backend, device):
         print(path)
 

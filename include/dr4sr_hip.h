@@ -736,6 +736,33 @@ int dr4sr_pairs_match(const int32_t* seqs, const int32_t* seq_len, int64_t n_seq
                       int32_t n_chunks, void* workspace, int64_t workspace_bytes, int32_t* n_match, int32_t* chosen, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Pattern mining for the regenerator (stage 1 of DR4SR, the first half of the reference's 1.Build_pretraining_dataset.py, lines 24-27:
+ * Seq2Pat(sequences, max_span = alpha).get_patterns(min_frequency = beta)), csrc/mine.hip.  Additive to ABI 10.  The rule:
+ *   pattern     : a tuple of k ids, 2 <= k <= alpha.
+ *   occurrence  : positions p_0 < ... < p_{k-1} of one sequence that hold the tuple's ids, with p_{k-1} - p_0 <= alpha - 1 (all items
+ *                 inside a window of alpha consecutive positions; csrc/mine.hip mine_reach is the one place of that bound).
+ *   frequency   : the number of sequences with at least one occurrence.
+ *   result      : every pattern with frequency >= beta, as rows of out_ids [cap, alpha] int32 (zero padded) and out_freq [cap] int32, in
+ *                 NO particular order (the set of rows is a pure function of the input, their order is not; the caller sorts).
+ * Sequences in ragged form: ids [n_ids] int32, every id >= 1, and seq_off [n_seq + 1] int64, sequence i = ids[seq_off[i] : seq_off[i+1]].
+ * n_out [1] int32 receives the number of patterns found even when it exceeds cap (rows past cap are not written: call again with a
+ * larger cap).  status [4] int64: [0] != 0 if the table filled up (the outputs are then meaningless), [1] the table's taken slots = the
+ * number of distinct tuples seen, [2] the sum over them of the distance from their home slot, [3] 0.
+ * The table: table_slots = 0 sizes it from n_ids * (2^(alpha-1) - 1), the number of (position, offset set) pairs, which no input can
+ * exceed, so it never fills up; an explicit power of two up to 2^30 is used as given (probing is bounded by the table's size, so a table
+ * that is too small ends the call quickly with status[0] set).  Workspace: 12 bytes per slot.
+ * Checked on the host before anything is launched: null pointers, negative or >= 2^31 sizes, beta < 1, cap < 0, table_slots not 0 or a
+ * power of two up to 2^30, n_ids * 2^(alpha-1) > 2^38 (DR4SR_E_ARG); alpha outside 2..10 (DR4SR_E_SHAPE); a null or too small
+ * workspace (DR4SR_E_WS).  NOT checked on the host: the contents of seq_off and ids.  On the device a position that does not lie inside
+ * 0 <= seq_off[i] <= position < seq_off[i+1] <= n_ids of the sequence a binary search finds for it starts no candidate, so nothing is
+ * read out of bounds; an id <= 0 is compared as given and can merge two patterns.  A sequence of n ids costs O(n) reads per candidate
+ * (the earlier-start test), which is why dr4sr_amd/mine.py refuses more than 4 096.  Three launches on `stream`, no host synchronisation. */
+int64_t dr4sr_mine_workspace_bytes(int64_t n_ids, int64_t n_seq, int32_t alpha, int64_t table_slots);
+int dr4sr_mine_patterns(const int32_t* ids, const int64_t* seq_off, int64_t n_ids, int64_t n_seq, int32_t alpha, int32_t beta,
+                        int64_t table_slots, void* workspace, int64_t workspace_bytes, int32_t* out_ids, int32_t* out_freq, int64_t cap,
+                        int32_t* n_out, int64_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Teacher-forced scoring of the regenerator (the forward and loss of DR4SR stage 2, the reference's 2.Pretrain_regenerator.py
  * Generator.forward + CrossEntropyLoss(ignore_index = 0) in eval mode: dropout off), csrc/regen_score.hip.  Additive to ABI 10.
  * A pair is (sequence s, pattern t); src row = [SOS] + s + [EOS], tgt row = [SOS] + t + [EOS], both padded with 0 to the widths of the
