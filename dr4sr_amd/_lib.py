@@ -112,6 +112,20 @@ class SasrecInputs(C.Structure):
     _fields_ = [("input_weight", _f32p), ("d_input_weight", _f32p)]
 
 
+LAYER_TENSORS = ("in_proj_weight", "in_proj_bias", "out_proj_weight", "out_proj_bias", "linear1_weight", "linear1_bias", "linear2_weight",
+                 "linear2_bias", "norm1_weight", "norm1_bias", "norm2_weight", "norm2_bias")
+
+
+class LayerWeights(C.Structure):
+    """mirror of `dr4sr_layer_weights` (include/dr4sr_hip.h): the 12 tensors of one encoder layer in the flat layout's order"""
+    _fields_ = [(n, _f32p) for n in LAYER_TENSORS]
+
+
+class LayerGrads(C.Structure):
+    """mirror of `dr4sr_layer_grads` (include/dr4sr_hip.h): the same 12, writable"""
+    _fields_ = [(n, _f32p) for n in LAYER_TENSORS]
+
+
 class MetaWeighting(C.Structure):
     """mirror of `dr4sr_meta_weighting` (include/dr4sr_hip.h)"""
     _fields_ = [("phi", _f32p), ("gumbel", _f32p), ("user_id", _i64p), ("gate_in", C.c_void_p), ("gate_out", C.c_void_p),
@@ -330,6 +344,18 @@ SYMBOLS = {
     "dr4sr_rank_metrics_accumulate": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p,
                                                 C.c_void_p]),
     "dr4sr_crash_line_set": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32]),           # measurement hook (include/dr4sr_hip_hooks.h)
+    # additive to ABI 10: the stateless encoder-layer op, sequence pooling and dropout on dense tensors (csrc/layer_op.hip)
+    "dr4sr_sasrec_layer_saved_floats": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "dr4sr_sasrec_layer_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "dr4sr_sasrec_layer_fwd": (C.c_int, [_f32p, C.c_void_p, C.c_int32, C.POINTER(LayerWeights), C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_float, C.c_float, C.c_uint64, C.c_uint32, C.c_int32, _f32p, _f32p, C.c_void_p]),
+    "dr4sr_sasrec_layer_bwd": (C.c_int, [_f32p, C.c_void_p, C.c_int32, C.POINTER(LayerWeights), C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_float, C.c_float, C.c_uint64, C.c_uint32, C.c_int32, _f32p, _f32p, _f32p,
+                                         C.POINTER(LayerGrads), C.c_void_p, C.c_int64, C.c_void_p]),
+    "dr4sr_seq_pool_fwd": (C.c_int, [_f32p, _i64p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _f32p, C.c_void_p]),
+    "dr4sr_seq_pool_bwd": (C.c_int, [_f32p, _i64p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _f32p, C.c_void_p]),
+    "dr4sr_dropout_apply": (C.c_int, [_f32p, C.c_int64, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, _f32p, C.c_void_p]),
+    "dr4sr_embed_gather_posadd_bwd": (C.c_int, [_f32p, _i64p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _f32p, C.c_void_p]),
 }
 
 _lib = None
@@ -341,7 +367,9 @@ class Dr4srError(RuntimeError):
 
 # additive entry points of ABI 10 that a library named by DR4SR_LIB_PATH (the OTHER build of an A/B run, tools/lib_ab.sh) may predate; the
 # tree's own library must export them like every other symbol
-_AFTER_PARENT_AB = ("dr4sr_sasrec_encode_w", "dr4sr_sasrec_encode_w_bwd", "dr4sr_mine_workspace_bytes", "dr4sr_mine_patterns")
+_AFTER_PARENT_AB = ("dr4sr_sasrec_encode_w", "dr4sr_sasrec_encode_w_bwd", "dr4sr_mine_workspace_bytes", "dr4sr_mine_patterns",
+                    "dr4sr_sasrec_layer_saved_floats", "dr4sr_sasrec_layer_workspace_bytes", "dr4sr_sasrec_layer_fwd", "dr4sr_sasrec_layer_bwd",
+                    "dr4sr_seq_pool_fwd", "dr4sr_seq_pool_bwd", "dr4sr_dropout_apply", "dr4sr_embed_gather_posadd_bwd")
 
 
 def load():

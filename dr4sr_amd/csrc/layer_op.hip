@@ -1,0 +1,811 @@
+// layer_op.hip — the stateless encoder-layer op (dr4sr_sasrec_layer_fwd / _bwd) and sequence pooling (dr4sr_seq_pool_fwd / _bwd) on dense
+// [B, L, D] tensors: what torch.ops.dr4sr_hip.sasrec_layer / seq_pool run.  One post-norm torch.nn.TransformerEncoderLayer as the
+// reference configures it (model/sasrec.py:21-30), with a general mask (key padding and / or causal); no plan, no device state words.
+//
+// Work distribution: one 256-thread workgroup per sequence, every activation of the layer in LDS (L <= 64 rows, zero rows behind L), GEMMs
+// on v_mfma_f32_32x32x2_f32 through common.h's 64-row tile helpers.  Attention runs per 64-column GROUP of the model width: at D = 64 a
+// group is both heads (head_dim 32), at D = 128 one head (head_dim 64), so q / k / v of a group are three [64][64] tiles and a head's scores
+// one [64][64] tile — the full [64][3 D] projection (96 KB at D = 128) is never resident.  LDS (floats):
+//     A [64][D + 4] | B [64][D + 4] | R = max([64][F + 4],  (3 + 2 HG) tiles of [64][68])        HG = heads per group
+// = 152 KB at D = 128 and 154 KB at D = 64 of the CU's 160 KB: one workgroup per CU.
+//
+// The backward recomputes nothing but the dropout masks (Philox is a pure function of (seed, step, site, element)) and the two LayerNorm
+// statistics: the forward saves qkv, the attention context, both LayerNorm inputs, the FFN pre-activation and the attention
+// probabilities (dr4sr_sasrec_layer_saved_floats).  Weight gradients: every workgroup writes ITS sum over the sequences it owns (b =
+// blockIdx.x, + gridDim.x, ... in that order) into its own slot of the workspace, a second launch adds the slots in index order — no float
+// atomics, the same bits on every call.
+#include "common.h"
+
+namespace lop {
+
+constexpr int LDT = 68;                // row stride of the [64][64] attention tiles
+constexpr int TILE = 64 * LDT;
+constexpr int MAX_SLOTS = 256;         // workgroups (= weight-gradient partial slots) of a backward launch
+
+template <int D, int F> struct Geo {
+    static constexpr int LDX = D + 4, LDF = F + 4, DH = D / 2, HG = 64 / DH, NG = D / 64, NV = D / 64;
+    static constexpr int R_FLOATS = (64 * LDF > (3 + 2 * HG) * TILE) ? 64 * LDF : (3 + 2 * HG) * TILE;
+    static constexpr int LDS_FLOATS = 2 * 64 * LDX + R_FLOATS + 64 + 4 * 64;
+    // one slot of weight-gradient partials: the 12 tensors in the flat layout's order
+    static constexpr int O_INW = 0, O_INB = O_INW + 3 * D * D, O_OW = O_INB + 3 * D, O_OB = O_OW + D * D, O_W1 = O_OB + D, O_B1 = O_W1 + F * D,
+                         O_W2 = O_B1 + F, O_B2 = O_W2 + D * F, O_N1W = O_B2 + D, O_N1B = O_N1W + D, O_N2W = O_N1B + D, O_N2B = O_N2W + D,
+                         NW = O_N2B + D;
+};
+
+__host__ __device__ inline int64_t saved_stride(int L, int D, int F) { return (((int64_t)L * (6 * D + F) + 2 * (int64_t)L * L) + 3) & ~(int64_t)3; }
+
+struct Args {
+    const float* x; const unsigned char* key_pad; int causal;
+    dr4sr_layer_weights w;
+    int B, L; float eps, p; uint64_t seed; uint32_t step; int layer;
+    float* y; float* saved;
+    const float* dy; float* dx; float* ws;
+};
+
+// rows [0, L) of a global [L][W] matrix -> LDS [64][ld], zero rows behind L
+template <int W>
+__device__ __forceinline__ void load_rows(float* __restrict__ dst, int ld, const float* __restrict__ src, int lds_, int L) {
+    load_tile<W>(dst, ld, src, lds_, 0, L);
+}
+// LDS [64][ld] rows [0, L) -> global [L][ldg]
+template <int W>
+__device__ __forceinline__ void store_rows(float* __restrict__ dst, int ldg, const float* __restrict__ src, int ld, int L) {
+    constexpr int C4 = W / 4;
+    for (int i = threadIdx.x; i < L * C4; i += 256) {
+        const int row = i / C4, c = (i % C4) * 4;
+        st4(dst + (size_t)row * ldg + c, ld4(src + row * ld + c));
+    }
+}
+// C[32 x 32] = sum over the 64 rows k of A[k][r] B[k][c]: the transposed-A product of the weight gradients and of dK / dV.  A and B point at
+// the tile's first column; lane (r, g) takes rows k in [32 g, 32 g + 32).  Result in the 32x32 C layout (row = (q & 3) + 8 (q >> 2) + 4 g).
+__device__ __forceinline__ f32x16 mma_tn(const float* __restrict__ A, int lda, const float* __restrict__ Bm, int ldb) {
+    const int lane = threadIdx.x & 63, r = lane & 31, g = lane >> 5;
+    f32x16 acc;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+    const float* a = A + (g * 32) * lda + r;
+    const float* b = Bm + (g * 32) * ldb + r;
+#pragma unroll 8
+    for (int k = 0; k < 32; ++k) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[k * lda], b[k * ldb], acc, 0, 0, 0);
+    return acc;
+}
+// common.h's mma_64xN_wT with the reduction loop unrolled by four float4 steps only: fully unrolled, the compiler hoists every weight load
+// of the GEMM in front of the first MFMA (KR / 2 x NTW dwords per lane), which with the accumulators in flight here runs out of registers
+// (1 - 2 KB of scratch per lane).  Measured, backward launches of two layers at B = 256, L = 50, d = 64 / 128: full 0.349 / 0.877 ms,
+// unroll 2: 0.299 / 0.625, unroll 4: 0.278 / 0.417, unroll 8 (scratch again at d = 64): 0.325 / 0.552 (NOTEBOOK)
+template <int KR, int NTW>
+__device__ __forceinline__ void mma_wT(const float* __restrict__ As, int lda, const float* __restrict__ W, int ldw, f32x16 (&acc)[NTW]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int r = lane & 31, g = lane >> 5, rh = w & 1, cg = w >> 1;
+    const float* arow = As + (rh * 32 + r) * lda + g * (KR / 2);
+    const float* wcol = W + (size_t)(g * (KR / 2)) * ldw + cg * 32 + r;
+#pragma unroll 4
+    for (int c = 0; c < KR / 2; c += 4) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(arow + c);
+#pragma unroll
+        for (int i = 0; i < NTW; ++i) {
+            const float* wp = wcol + (size_t)c * ldw + 64 * i;
+            const float b0 = wp[0], b1 = wp[ldw], b2 = wp[2 * ldw], b3 = wp[3 * ldw];
+            acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b0, acc[i], 0, 0, 0);
+            acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b1, acc[i], 0, 0, 0);
+            acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b2, acc[i], 0, 0, 0);
+            acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b3, acc[i], 0, 0, 0);
+        }
+    }
+}
+__device__ __forceinline__ void wput(float* __restrict__ p, float v, bool first) { *p = first ? v : *p + v; }
+// weight-gradient partial  out[M x N] (row stride ldo) = A^T B  over the token rows; 32x32 tiles dealt to the four waves
+template <int M, int N>
+__device__ __forceinline__ void wgrad_tn(float* __restrict__ out, int ldo, const float* __restrict__ A, int lda, const float* __restrict__ Bm, int ldb,
+                                         bool first) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, g = lane >> 5;
+    constexpr int NT = N / 32, TILES = (M / 32) * NT;
+    for (int t = w; t < TILES; t += 4) {
+        const int mt = t / NT, nt = t % NT;
+        const f32x16 acc = mma_tn(A + mt * 32, lda, Bm + nt * 32, ldb);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int row = mt * 32 + (q & 3) + 8 * (q >> 2) + 4 * g;
+            wput(out + (size_t)row * ldo + nt * 32 + r, acc[q], first);
+        }
+    }
+}
+// column sums over rows [0, L) of an LDS matrix, rows added in index order: out[c] for c < W
+__device__ __forceinline__ void colsum(float* __restrict__ out, const float* __restrict__ S, int ld, int W, int L, bool first) {
+    for (int c = threadIdx.x; c < W; c += 256) {
+        float s = 0.f;
+        for (int row = 0; row < L; ++row) s += S[row * ld + c];
+        wput(out + c, s, first);
+    }
+}
+__device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
+__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// does query i of this sequence admit key j?  kp = LDS flags (1: padded or behind L)
+__device__ __forceinline__ bool admit(const float* kp, int causal, int i, int j) { return kp[j] == 0.f && (!causal || j <= i); }
+
+// =================================================================================================================== forward
+template <int D, int F>
+__global__ __launch_bounds__(256) void k_layer_fwd(const Args a) {
+    using G = Geo<D, F>;
+    constexpr int LDX = G::LDX, LDF = G::LDF, DH = G::DH, HG = G::HG, NV = G::NV;
+    extern __shared__ __align__(16) float lds[];
+    float* As = lds;                       // x, then y1
+    float* Bs = As + 64 * LDX;             // attention context, then the FFN output
+    float* R = Bs + 64 * LDX;
+    float* kp = R + G::R_FLOATS;
+    float *Qs = R, *Ks = R + TILE, *Vs = R + 2 * TILE, *Ss = R + 3 * TILE;
+    const int tid = threadIdx.x, L = a.L;
+    const RngKey rk = make_rng(a.seed, a.step, a.p);
+    const bool drop = a.p > 0.f;
+    const uint32_t s_attn = DR4SR_SITE_ATTN + 4 * a.layer, s_proj = DR4SR_SITE_PROJ + 4 * a.layer, s_act = DR4SR_SITE_ACT + 4 * a.layer,
+                   s_ffn = DR4SR_SITE_FFN + 4 * a.layer;
+    const float scale = 1.0f / sqrtf((float)DH);
+    const int64_t SS = saved_stride(L, D, F);
+    const int wv = tid >> 6, cg = wv >> 1;
+
+    for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+        float* sv = a.saved ? a.saved + (size_t)b * SS : nullptr;
+        float* sv_qkv = sv, *sv_ctx = sv + (size_t)L * 3 * D, *sv_u1 = sv_ctx + (size_t)L * D, *sv_h = sv_u1 + (size_t)L * D,
+              *sv_u2 = sv_h + (size_t)L * F, *sv_p = sv_u2 + (size_t)L * D;
+        load_rows<D>(As, LDX, a.x + (size_t)b * L * D, D, L);
+        if (tid < 64) kp[tid] = (tid >= L || (a.key_pad && a.key_pad[(size_t)b * L + tid])) ? 1.f : 0.f;
+        __syncthreads();
+        // ---- attention, one 64-column group at a time
+        for (int g = 0; g < G::NG; ++g) {
+#pragma unroll
+            for (int m = 0; m < 3; ++m) {
+                f32x16 acc[1];
+                acc_zero(acc);
+                mma_64xN<D, 1>(As, LDX, a.w.in_proj_weight + (size_t)(m * D + g * 64) * D, acc);
+                acc_to_lds<1>(acc, R + m * TILE, LDT, a.w.in_proj_bias + m * D + g * 64);
+            }
+            __syncthreads();
+            if (sv)
+                for (int m = 0; m < 3; ++m) store_rows<64>(sv_qkv + m * D + g * 64, 3 * D, R + m * TILE, LDT, L);
+#pragma unroll
+            for (int hh = 0; hh < HG; ++hh) {
+                f32x16 acc[1];
+                acc_zero(acc);
+                mma_64xN_ld<DH, 1>(Qs + hh * DH, LDT, Ks + hh * DH, LDT, acc);
+                acc_to_lds<1>(acc, Ss + hh * TILE, LDT, nullptr);
+            }
+            __syncthreads();
+            // softmax + dropout: 4 lanes per query row, lane t takes keys t, t + 4, ...
+            for (int hh = 0; hh < HG; ++hh) {
+                const int i = tid >> 2, t = tid & 3, h = g * HG + hh;
+                float* srow = Ss + hh * TILE + i * LDT;
+                float v[16], mx = -INFINITY;
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                    const int j = t + 4 * c;
+                    v[c] = admit(kp, a.causal, i, j) ? srow[j] * scale : -INFINITY;
+                    mx = fmaxf(mx, v[c]);
+                }
+                mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
+                mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
+                float sum = 0.f;
+#pragma unroll
+                for (int c = 0; c < 16; ++c) { v[c] = (mx == -INFINITY) ? 0.f : expf(v[c] - mx); sum += v[c]; }
+                sum += __shfl_xor(sum, 1, 64);
+                sum += __shfl_xor(sum, 2, 64);
+                const float inv = (mx == -INFINITY || i >= L) ? 0.f : 1.0f / sum;      // no admissible key: a zero context
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                    const int j = t + 4 * c;
+                    float pv = v[c] * inv;
+                    if (i < L && j < L) {
+                        const size_t e = ((size_t)(b * 2 + h) * L + i) * L + j;
+                        if (sv) sv_p[((size_t)h * L + i) * L + j] = pv;
+                        if (drop) pv *= drop1(rk, s_attn, e);
+                    }
+                    srow[j] = pv;
+                }
+            }
+            __syncthreads();
+            {
+                f32x16 acc[1];
+                acc_zero(acc);
+                mma_64xN_wT<64, 1>(Ss + ((cg * 32) / DH) * TILE, LDT, Vs, LDT, acc);
+                acc_to_lds<1>(acc, Bs + g * 64, LDX, nullptr);
+            }
+            __syncthreads();
+        }
+        if (sv) store_rows<D>(sv_ctx, D, Bs, LDX, L);
+        // ---- out_proj -> R [64][LDX]
+        {
+            f32x16 acc[D / 64];
+            acc_zero(acc);
+            mma_64xN<D, D / 64>(Bs, LDX, a.w.out_proj_weight, acc);
+            acc_to_lds<D / 64>(acc, R, LDX, a.w.out_proj_bias);
+        }
+        __syncthreads();
+        // ---- u1 = x + drop(o), y1 = LN1(u1) -> As : 16 lanes per row
+        for (int row = tid >> 4; row < 64; row += 16) {
+            const int j16 = tid & 15;
+            float4 u[NV];
+            if (row < L) {
+#pragma unroll
+                for (int j = 0; j < NV; ++j) {
+                    const int c = 4 * j16 + 64 * j;
+                    float4 o = ld4(R + row * LDX + c);
+                    if (drop) o = mul4(o, drop4(rk, s_proj, ((uint64_t)b * L + row) * D + c));
+                    u[j] = add4(ld4(As + row * LDX + c), o);
+                    if (sv) st4(sv_u1 + (size_t)row * D + c, u[j]);
+                }
+                float mean, rstd;
+                ln_stats16<NV>(u, mean, rstd, a.eps);
+#pragma unroll
+                for (int j = 0; j < NV; ++j) {
+                    const int c = 4 * j16 + 64 * j;
+                    const float4 gm = ld4(a.w.norm1_weight + c), bt = ld4(a.w.norm1_bias + c);
+                    st4(As + row * LDX + c, make_float4((u[j].x - mean) * rstd * gm.x + bt.x, (u[j].y - mean) * rstd * gm.y + bt.y,
+                                                        (u[j].z - mean) * rstd * gm.z + bt.z, (u[j].w - mean) * rstd * gm.w + bt.w));
+                }
+            }
+        }
+        __syncthreads();
+        // ---- FFN
+        {
+            f32x16 acc[F / 64];
+            acc_zero(acc);
+            mma_64xN<D, F / 64>(As, LDX, a.w.linear1_weight, acc);
+            acc_to_lds<F / 64>(acc, R, LDF, a.w.linear1_bias);
+        }
+        __syncthreads();
+        for (int i = tid; i < 64 * (F / 4); i += 256) {
+            const int row = i / (F / 4), c = (i % (F / 4)) * 4;
+            float4 hv = ld4(R + row * LDF + c);
+            if (row < L) {
+                if (sv) st4(sv_h + (size_t)row * F + c, hv);
+                hv = make_float4(gelu_erf(hv.x), gelu_erf(hv.y), gelu_erf(hv.z), gelu_erf(hv.w));
+                if (drop) hv = mul4(hv, drop4(rk, s_act, ((uint64_t)b * L + row) * F + c));
+            } else hv = make_float4(0.f, 0.f, 0.f, 0.f);
+            st4(R + row * LDF + c, hv);
+        }
+        __syncthreads();
+        {
+            f32x16 acc[D / 64];
+            acc_zero(acc);
+            mma_64xN<F, D / 64>(R, LDF, a.w.linear2_weight, acc);
+            acc_to_lds<D / 64>(acc, Bs, LDX, a.w.linear2_bias);
+        }
+        __syncthreads();
+        for (int row = tid >> 4; row < 64; row += 16) {
+            const int j16 = tid & 15;
+            float4 u[NV];
+            if (row < L) {
+#pragma unroll
+                for (int j = 0; j < NV; ++j) {
+                    const int c = 4 * j16 + 64 * j;
+                    float4 f = ld4(Bs + row * LDX + c);
+                    if (drop) f = mul4(f, drop4(rk, s_ffn, ((uint64_t)b * L + row) * D + c));
+                    u[j] = add4(ld4(As + row * LDX + c), f);
+                    if (sv) st4(sv_u2 + (size_t)row * D + c, u[j]);
+                }
+                float mean, rstd;
+                ln_stats16<NV>(u, mean, rstd, a.eps);
+#pragma unroll
+                for (int j = 0; j < NV; ++j) {
+                    const int c = 4 * j16 + 64 * j;
+                    const float4 gm = ld4(a.w.norm2_weight + c), bt = ld4(a.w.norm2_bias + c);
+                    st4(a.y + ((size_t)b * L + row) * D + c, make_float4((u[j].x - mean) * rstd * gm.x + bt.x, (u[j].y - mean) * rstd * gm.y + bt.y,
+                                                                         (u[j].z - mean) * rstd * gm.z + bt.z, (u[j].w - mean) * rstd * gm.w + bt.w));
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// =================================================================================================================== backward
+// LayerNorm statistics of the rows of U (16 lanes per row) -> st[row] = (mean, rstd)
+template <int D>
+__device__ __forceinline__ void ln_stats_rows(const float* __restrict__ U, int ld, float* __restrict__ st, int L, float eps) {
+    constexpr int NV = D / 64;
+    for (int row = threadIdx.x >> 4; row < 64; row += 16) {
+        const int j16 = threadIdx.x & 15;
+        float4 u[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) u[j] = ld4(U + row * ld + 4 * j16 + 64 * j);
+        float mean, rstd;
+        ln_stats16<NV>(u, mean, rstd, eps);
+        if (j16 == 0) { st[2 * row] = row < L ? mean : 0.f; st[2 * row + 1] = row < L ? rstd : 0.f; }
+    }
+}
+// d gamma[c] = sum_rows dz xhat, d beta[c] = sum_rows dz (rows in index order)
+template <int D>
+__device__ __forceinline__ void ln_affine_grads(float* __restrict__ dgam, float* __restrict__ dbet, const float* __restrict__ dZ,
+                                                const float* __restrict__ U, int ld, const float* __restrict__ st, int L, bool first) {
+    for (int c = threadIdx.x; c < D; c += 256) {
+        float sg = 0.f, sb = 0.f;
+        for (int row = 0; row < L; ++row) {
+            const float dz = dZ[row * ld + c];
+            sg += dz * (U[row * ld + c] - st[2 * row]) * st[2 * row + 1];
+            sb += dz;
+        }
+        wput(dgam + c, sg, first);
+        wput(dbet + c, sb, first);
+    }
+}
+
+template <int D, int F>
+__global__ __launch_bounds__(256) void k_layer_bwd(const Args a) {
+    using G = Geo<D, F>;
+    constexpr int LDX = G::LDX, LDF = G::LDF, DH = G::DH, HG = G::HG, NV = G::NV;
+    extern __shared__ __align__(16) float lds[];
+    float* As = lds;                       // dy -> du2 -> dy1 -> du1 -> d ctx
+    float* Bs = As + 64 * LDX;             // u2 -> d f2 -> y1 -> u1 -> d o -> x
+    float* R = Bs + 64 * LDX;
+    float* kp = R + G::R_FLOATS;
+    float* st1 = kp + 64;
+    float* st2 = st1 + 128;
+    float *Qs = R, *Ks = R + TILE, *Vs = R + 2 * TILE, *Ss = R + 3 * TILE, *Ds = R + (3 + HG) * TILE;
+    const int tid = threadIdx.x, L = a.L;
+    const RngKey rk = make_rng(a.seed, a.step, a.p);
+    const bool drop = a.p > 0.f;
+    const uint32_t s_attn = DR4SR_SITE_ATTN + 4 * a.layer, s_proj = DR4SR_SITE_PROJ + 4 * a.layer, s_act = DR4SR_SITE_ACT + 4 * a.layer,
+                   s_ffn = DR4SR_SITE_FFN + 4 * a.layer;
+    const float scale = 1.0f / sqrtf((float)DH);
+    const int64_t SS = saved_stride(L, D, F);
+    const int lane = tid & 63, wv = tid >> 6, r32 = lane & 31, g32 = lane >> 5, rh = wv & 1, cg = wv >> 1;
+    float* ws = a.ws + (size_t)blockIdx.x * G::NW;
+
+    for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+        const bool first = b == (int)blockIdx.x;
+        const float* sv = a.saved + (size_t)b * SS;
+        const float *sv_qkv = sv, *sv_ctx = sv + (size_t)L * 3 * D, *sv_u1 = sv_ctx + (size_t)L * D, *sv_h = sv_u1 + (size_t)L * D,
+                    *sv_u2 = sv_h + (size_t)L * F, *sv_p = sv_u2 + (size_t)L * D;
+        float* dxb = a.dx + (size_t)b * L * D;
+        // ---------------------------------------------------------------- A: LayerNorm 2 and the FFN
+        load_rows<D>(As, LDX, a.dy + (size_t)b * L * D, D, L);
+        load_rows<D>(Bs, LDX, sv_u2, D, L);
+        if (tid < 64) kp[tid] = (tid >= L || (a.key_pad && a.key_pad[(size_t)b * L + tid])) ? 1.f : 0.f;
+        __syncthreads();
+        ln_stats_rows<D>(Bs, LDX, st2, L, a.eps);
+        __syncthreads();
+        ln_affine_grads<D>(ws + G::O_N2W, ws + G::O_N2B, As, Bs, LDX, st2, L, first);
+        __syncthreads();
+        // du2 -> As, d f2 = du2 * mask -> Bs
+        for (int row = tid >> 4; row < 64; row += 16) {
+            const int j16 = tid & 15;
+            float4 dz[NV], u[NV], gm[NV], dg[NV], db[NV];
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const int c = 4 * j16 + 64 * j;
+                dz[j] = ld4(As + row * LDX + c); u[j] = ld4(Bs + row * LDX + c); gm[j] = ld4(a.w.norm2_weight + c);
+                dg[j] = db[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            ln_bwd_row<NV>(dz, u, st2[2 * row], st2[2 * row + 1], gm, dg, db);
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const int c = 4 * j16 + 64 * j;
+                st4(As + row * LDX + c, dz[j]);
+                float4 df = dz[j];
+                if (drop && row < L) df = mul4(df, drop4(rk, s_ffn, ((uint64_t)b * L + row) * D + c));
+                st4(Bs + row * LDX + c, df);
+            }
+        }
+        // hd = drop(gelu(hpre)) -> R
+        for (int i = tid; i < 64 * (F / 4); i += 256) {
+            const int row = i / (F / 4), c = (i % (F / 4)) * 4;
+            float4 hv = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (row < L) {
+                hv = ld4(sv_h + (size_t)row * F + c);
+                hv = make_float4(gelu_erf(hv.x), gelu_erf(hv.y), gelu_erf(hv.z), gelu_erf(hv.w));
+                if (drop) hv = mul4(hv, drop4(rk, s_act, ((uint64_t)b * L + row) * F + c));
+            }
+            st4(R + row * LDF + c, hv);
+        }
+        __syncthreads();
+        wgrad_tn<D, F>(ws + G::O_W2, F, Bs, LDX, R, LDF, first);
+        colsum(ws + G::O_B2, Bs, LDX, D, L, first);
+        __syncthreads();
+        // R := d hd / d hpre factor = mask * gelu'(hpre); then d hpre = (d f2 W2) * R in place
+        for (int i = tid; i < 64 * (F / 4); i += 256) {
+            const int row = i / (F / 4), c = (i % (F / 4)) * 4;
+            float4 fv = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (row < L) {
+                const float4 hv = ld4(sv_h + (size_t)row * F + c);
+                fv = make_float4(gelu_erf_grad(hv.x), gelu_erf_grad(hv.y), gelu_erf_grad(hv.z), gelu_erf_grad(hv.w));
+                if (drop) fv = mul4(fv, drop4(rk, s_act, ((uint64_t)b * L + row) * F + c));
+            }
+            st4(R + row * LDF + c, fv);
+        }
+        {
+            f32x16 acc[F / 64];
+            acc_zero(acc);
+            mma_wT<D, F / 64>(Bs, LDX, a.w.linear2_weight, F, acc);
+            __syncthreads();                                   // the factor is in R, every wave is done reading d f2 from Bs
+#pragma unroll
+            for (int i = 0; i < F / 64; ++i)
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    float* pp = R + (rh * 32 + (q & 3) + 8 * (q >> 2) + 4 * g32) * LDF + (cg + 2 * i) * 32 + r32;
+                    *pp *= acc[i][q];
+                }
+        }
+        // y1 = LN1(u1) -> Bs, statistics -> st1
+        for (int row = tid >> 4; row < 64; row += 16) {
+            const int j16 = tid & 15;
+            float4 u[NV];
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const int c = 4 * j16 + 64 * j;
+                u[j] = row < L ? ld4(sv_u1 + (size_t)row * D + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            float mean, rstd;
+            ln_stats16<NV>(u, mean, rstd, a.eps);
+            if (j16 == 0) { st1[2 * row] = row < L ? mean : 0.f; st1[2 * row + 1] = row < L ? rstd : 0.f; }
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const int c = 4 * j16 + 64 * j;
+                float4 yv = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (row < L) {
+                    const float4 gm = ld4(a.w.norm1_weight + c), bt = ld4(a.w.norm1_bias + c);
+                    yv = make_float4((u[j].x - mean) * rstd * gm.x + bt.x, (u[j].y - mean) * rstd * gm.y + bt.y,
+                                     (u[j].z - mean) * rstd * gm.z + bt.z, (u[j].w - mean) * rstd * gm.w + bt.w);
+                }
+                st4(Bs + row * LDX + c, yv);
+            }
+        }
+        __syncthreads();
+        wgrad_tn<F, D>(ws + G::O_W1, D, R, LDF, Bs, LDX, first);
+        colsum(ws + G::O_B1, R, LDF, F, L, first);
+        {
+            f32x16 acc[D / 64];
+            acc_zero(acc);
+            mma_wT<F, D / 64>(R, LDF, a.w.linear1_weight, D, acc);
+#pragma unroll
+            for (int i = 0; i < D / 64; ++i)
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    float* pp = As + (rh * 32 + (q & 3) + 8 * (q >> 2) + 4 * g32) * LDX + (cg + 2 * i) * 32 + r32;
+                    *pp += acc[i][q];                           // dy1 = d hpre W1 + du2
+                }
+        }
+        __syncthreads();
+        // ---------------------------------------------------------------- B: LayerNorm 1 and out_proj
+        load_rows<D>(Bs, LDX, sv_u1, D, L);
+        __syncthreads();
+        ln_affine_grads<D>(ws + G::O_N1W, ws + G::O_N1B, As, Bs, LDX, st1, L, first);
+        __syncthreads();
+        for (int row = tid >> 4; row < 64; row += 16) {
+            const int j16 = tid & 15;
+            float4 dz[NV], u[NV], gm[NV], dg[NV], db[NV];
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const int c = 4 * j16 + 64 * j;
+                dz[j] = ld4(As + row * LDX + c); u[j] = ld4(Bs + row * LDX + c); gm[j] = ld4(a.w.norm1_weight + c);
+                dg[j] = db[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            ln_bwd_row<NV>(dz, u, st1[2 * row], st1[2 * row + 1], gm, dg, db);
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const int c = 4 * j16 + 64 * j;
+                if (row < L) st4(dxb + (size_t)row * D + c, dz[j]);            // the residual branch of dx; the attention branch is added at the end
+                float4 dv = dz[j];
+                if (drop && row < L) dv = mul4(dv, drop4(rk, s_proj, ((uint64_t)b * L + row) * D + c));
+                st4(Bs + row * LDX + c, dv);
+            }
+        }
+        load_rows<D>(R, LDX, sv_ctx, D, L);
+        __syncthreads();
+        wgrad_tn<D, D>(ws + G::O_OW, D, Bs, LDX, R, LDX, first);
+        colsum(ws + G::O_OB, Bs, LDX, D, L, first);
+        {
+            f32x16 acc[D / 64];
+            acc_zero(acc);
+            mma_wT<D, D / 64>(Bs, LDX, a.w.out_proj_weight, D, acc);
+            __syncthreads();
+            acc_to_lds<D / 64>(acc, As, LDX, nullptr);        // d ctx
+        }
+        load_rows<D>(Bs, LDX, a.x + (size_t)b * L * D, D, L);
+        // ---------------------------------------------------------------- C: attention, group by group
+        f32x16 dxacc[D / 64];
+        acc_zero(dxacc);
+        for (int g = 0; g < G::NG; ++g) {
+            __syncthreads();
+            for (int m = 0; m < 3; ++m) load_rows<64>(R + m * TILE, LDT, sv_qkv + m * D + g * 64, 3 * D, L);
+            for (int i = tid; i < HG * 64 * 64; i += 256) {
+                const int hh = i >> 12, qi = (i >> 6) & 63, j = i & 63;
+                Ss[hh * TILE + qi * LDT + j] = (qi < L && j < L) ? sv_p[((size_t)(g * HG + hh) * L + qi) * L + j] : 0.f;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int hh = 0; hh < HG; ++hh) {
+                f32x16 acc[1];
+                acc_zero(acc);
+                mma_64xN_ld<DH, 1>(As + g * 64 + hh * DH, LDX, Vs + hh * DH, LDT, acc);
+                acc_to_lds<1>(acc, Ds + hh * TILE, LDT, nullptr);
+            }
+            __syncthreads();
+            // Ss := p * mask (what multiplied v), Ds := scale * p * (dp - <dp, p>)
+            for (int hh = 0; hh < HG; ++hh) {
+                const int i = tid >> 2, t = tid & 3, h = g * HG + hh;
+                float* prow = Ss + hh * TILE + i * LDT;
+                float* drow = Ds + hh * TILE + i * LDT;
+                float pv[16], dp[16], dot = 0.f;
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                    const int j = t + 4 * c;
+                    pv[c] = prow[j];
+                    float m = 1.f;
+                    if (drop && i < L && j < L) m = drop1(rk, s_attn, ((size_t)(b * 2 + h) * L + i) * L + j);
+                    dp[c] = drow[j] * m;
+                    dot += dp[c] * pv[c];
+                    prow[j] = pv[c] * m;
+                }
+                dot += __shfl_xor(dot, 1, 64);
+                dot += __shfl_xor(dot, 2, 64);
+#pragma unroll
+                for (int c = 0; c < 16; ++c) drow[t + 4 * c] = scale * pv[c] * (dp[c] - dot);
+            }
+            __syncthreads();
+            {
+                const int hd = (cg * 32) / DH;                 // head (inside the group) of this wave's 32 output columns
+                const f32x16 dv = mma_tn(Ss + hd * TILE + rh * 32, LDT, As + g * 64 + cg * 32, LDX);
+                const f32x16 dk = mma_tn(Ds + hd * TILE + rh * 32, LDT, Qs + cg * 32, LDT);
+                f32x16 dq[1];
+                acc_zero(dq);
+                mma_64xN_wT<64, 1>(Ds + hd * TILE, LDT, Ks, LDT, dq);
+                __syncthreads();
+                f32x16 t1[1];
+                acc_to_lds<1>(dq, Qs, LDT, nullptr);
+                t1[0] = dk; acc_to_lds<1>(t1, Ks, LDT, nullptr);
+                t1[0] = dv; acc_to_lds<1>(t1, Vs, LDT, nullptr);
+            }
+            __syncthreads();
+            for (int m = 0; m < 3; ++m) {
+                wgrad_tn<64, D>(ws + G::O_INW + (size_t)(m * D + g * 64) * D, D, R + m * TILE, LDT, Bs, LDX, first);
+                colsum(ws + G::O_INB + m * D + g * 64, R + m * TILE, LDT, 64, L, first);
+                mma_wT<64, D / 64>(R + m * TILE, LDT, a.w.in_proj_weight + (size_t)(m * D + g * 64) * D, D, dxacc);
+            }
+        }
+        __syncthreads();                                       // makes this workgroup's residual-branch stores to dx visible to it
+#pragma unroll
+        for (int i = 0; i < D / 64; ++i)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int row = rh * 32 + (q & 3) + 8 * (q >> 2) + 4 * g32;
+                if (row < L) dxb[(size_t)row * D + (cg + 2 * i) * 32 + r32] += dxacc[i][q];
+            }
+        __syncthreads();
+    }
+}
+
+// sums the workgroups' partial slots in index order and writes the 12 gradients
+template <int D, int F>
+__global__ void k_layer_reduce(const float* __restrict__ ws, int n_slots, dr4sr_layer_grads dw) {
+    using G = Geo<D, F>;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= G::NW) return;
+    const float s = det_sum(ws + e, n_slots, G::NW);
+    float* dst; int o;
+    if (e < G::O_INB) { dst = dw.in_proj_weight; o = G::O_INW; }
+    else if (e < G::O_OW) { dst = dw.in_proj_bias; o = G::O_INB; }
+    else if (e < G::O_OB) { dst = dw.out_proj_weight; o = G::O_OW; }
+    else if (e < G::O_W1) { dst = dw.out_proj_bias; o = G::O_OB; }
+    else if (e < G::O_B1) { dst = dw.linear1_weight; o = G::O_W1; }
+    else if (e < G::O_W2) { dst = dw.linear1_bias; o = G::O_B1; }
+    else if (e < G::O_B2) { dst = dw.linear2_weight; o = G::O_W2; }
+    else if (e < G::O_N1W) { dst = dw.linear2_bias; o = G::O_B2; }
+    else if (e < G::O_N1B) { dst = dw.norm1_weight; o = G::O_N1W; }
+    else if (e < G::O_N2W) { dst = dw.norm1_bias; o = G::O_N1B; }
+    else if (e < G::O_N2B) { dst = dw.norm2_weight; o = G::O_N2W; }
+    else { dst = dw.norm2_bias; o = G::O_N2B; }
+    dst[e - o] = s;
+}
+
+// =================================================================================================================== pooling
+__device__ __forceinline__ int clamp_len(const int64_t* seqlen, int b, int L) {
+    const int64_t n = seqlen[b];
+    return n < 0 ? 0 : n > L ? L : (int)n;
+}
+// ORIGIN: one thread per element of [B, L, D]; LAST / MEAN: one thread per element of [B, D]
+__global__ void k_pool_fwd(const float* __restrict__ x, const int64_t* __restrict__ seqlen, int pooling, int64_t B, int L, int D,
+                           float* __restrict__ out) {
+    const int64_t n = pooling == DR4SR_POOL_ORIGIN ? B * L * D : B * D;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+        if (pooling == DR4SR_POOL_ORIGIN) {
+            const int b = (int)(e / ((int64_t)L * D)), pos = (int)((e / D) % L);
+            out[e] = pos < clamp_len(seqlen, b, L) ? x[e] : 0.f;
+        } else {
+            const int b = (int)(e / D), c = (int)(e % D), n_ = clamp_len(seqlen, b, L);
+            const float* xb = x + (size_t)b * L * D + c;
+            float v = 0.f;
+            if (n_ > 0) {
+                if (pooling == DR4SR_POOL_LAST) v = xb[(size_t)(n_ - 1) * D];
+                else { for (int pos = 0; pos < n_; ++pos) v += xb[(size_t)pos * D]; v /= (float)n_; }
+            }
+            out[e] = v;
+        }
+    }
+}
+__global__ void k_pool_bwd(const float* __restrict__ dout, const int64_t* __restrict__ seqlen, int pooling, int64_t B, int L, int D,
+                           float* __restrict__ dx) {
+    const int64_t n = B * L * D;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+        const int b = (int)(e / ((int64_t)L * D)), pos = (int)((e / D) % L), c = (int)(e % D), n_ = clamp_len(seqlen, b, L);
+        float v = 0.f;
+        if (pooling == DR4SR_POOL_ORIGIN) v = pos < n_ ? dout[e] : 0.f;
+        else if (pooling == DR4SR_POOL_LAST) v = pos == n_ - 1 ? dout[(size_t)b * D + c] : 0.f;
+        else v = pos < n_ ? dout[(size_t)b * D + c] / (float)n_ : 0.f;
+        dx[e] = v;
+    }
+}
+
+__global__ void k_dropout_apply(const float* __restrict__ x, int64_t n4, float p, uint64_t seed, uint32_t step, uint32_t site,
+                                float* __restrict__ out) {
+    const RngKey rk = make_rng(seed, step, p);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        float4 v = ld4(x + i * 4);
+        if (p > 0.f) v = mul4(v, drop4(rk, site, (uint64_t)i * 4));
+        st4(out + i * 4, v);
+    }
+}
+
+// backward of embed_gather_posadd: dE[idx[t]] += dx[t] (PAD id 0 and ids outside the table pass nothing), dP[pos] = sum_b dx[b, pos]
+__global__ void k_embed_bwd_table(const float* __restrict__ dx, const int64_t* __restrict__ idx, int64_t T, int D, int N, float* __restrict__ dE) {
+    const int C4 = D / 4;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < T * C4; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t t = e / C4, id = idx[t];
+        if (id <= 0 || id >= N) continue;
+        const int c = (int)(e % C4) * 4;
+        const float4 v = ld4(dx + t * D + c);
+        float* d = dE + id * D + c;
+        atomicAdd(d, v.x); atomicAdd(d + 1, v.y); atomicAdd(d + 2, v.z); atomicAdd(d + 3, v.w);
+    }
+}
+__global__ void k_embed_bwd_pos(const float* __restrict__ dx, int B, int LD, float* __restrict__ dP) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < LD) dP[e] = det_sum(dx + e, B, (size_t)LD);
+}
+
+// =================================================================================================================== host
+static int shape_check(int64_t B, int L, int D, int H, int F) {
+    if (B < 0 || L < 1 || D < 1 || H < 1 || F < 1) return DR4SR_E_ARG;
+    if (L > 64 || D % H) return DR4SR_E_SHAPE;
+    const int dh = D / H;
+    if (!((D == 64 && (F == 128 || F == 256) && dh == 32) || (D == 128 && F == 128 && dh == 64))) return DR4SR_E_SHAPE;
+    if (B * (int64_t)L * L >= ((int64_t)1 << 30)) return DR4SR_E_ARG;      // 32-bit sequence x head index of the attention dropout stream
+    return 0;
+}
+static int64_t slot_floats(int D, int F) { return 4 * (int64_t)D * D + 2 * (int64_t)D * F + 9 * (int64_t)D + F; }
+static int n_slots(int64_t B) { return B < MAX_SLOTS ? (int)B : MAX_SLOTS; }
+
+template <int D, int F>
+static int launch_fwd(const Args& a, hipStream_t st) {
+    const size_t lds = Geo<D, F>::LDS_FLOATS * sizeof(float);
+    big_lds(k_layer_fwd<D, F>, lds);
+    hipLaunchKernelGGL((k_layer_fwd<D, F>), dim3((unsigned)(a.B < 65535 ? a.B : 65535)), dim3(256), lds, st, a);
+    return DR4SR_LAUNCH_CHECK();
+}
+template <int D, int F>
+static int launch_bwd(const Args& a, const dr4sr_layer_grads& dw, hipStream_t st) {
+    static_assert(Geo<D, F>::NW == 4 * D * D + 2 * D * F + 9 * D + F, "slot size");
+    const size_t lds = Geo<D, F>::LDS_FLOATS * sizeof(float);
+    big_lds(k_layer_bwd<D, F>, lds);
+    const int ns = n_slots(a.B);
+    hipLaunchKernelGGL((k_layer_bwd<D, F>), dim3(ns), dim3(256), lds, st, a);
+    int rc = DR4SR_LAUNCH_CHECK();
+    if (rc) return rc;
+    hipLaunchKernelGGL((k_layer_reduce<D, F>), dim3((Geo<D, F>::NW + 255) / 256), dim3(256), 0, st, a.ws, ns, dw);
+    return DR4SR_LAUNCH_CHECK();
+}
+
+}  // namespace lop
+
+extern "C" int64_t dr4sr_sasrec_layer_saved_floats(int64_t B, int32_t L, int32_t D, int32_t H, int32_t F) {
+    const int rc = lop::shape_check(B, L, D, H, F);
+    if (rc) return rc;
+    return B * lop::saved_stride(L, D, F);
+}
+
+extern "C" int64_t dr4sr_sasrec_layer_workspace_bytes(int64_t B, int32_t L, int32_t D, int32_t H, int32_t F) {
+    const int rc = lop::shape_check(B, L, D, H, F);
+    if (rc) return rc;
+    return (int64_t)lop::n_slots(B) * lop::slot_floats(D, F) * (int64_t)sizeof(float);
+}
+
+static bool weights_ok(const dr4sr_layer_weights* w) {
+    return w && w->in_proj_weight && w->in_proj_bias && w->out_proj_weight && w->out_proj_bias && w->linear1_weight && w->linear1_bias &&
+           w->linear2_weight && w->linear2_bias && w->norm1_weight && w->norm1_bias && w->norm2_weight && w->norm2_bias;
+}
+static bool grads_ok(const dr4sr_layer_grads* w) {
+    return w && w->in_proj_weight && w->in_proj_bias && w->out_proj_weight && w->out_proj_bias && w->linear1_weight && w->linear1_bias &&
+           w->linear2_weight && w->linear2_bias && w->norm1_weight && w->norm1_bias && w->norm2_weight && w->norm2_bias;
+}
+
+extern "C" int dr4sr_sasrec_layer_fwd(const float* x, const uint8_t* key_pad, int32_t causal, const dr4sr_layer_weights* w, int64_t B, int32_t L,
+                                      int32_t D, int32_t H, int32_t F, float eps, float p_drop, uint64_t seed, uint32_t step, int32_t layer,
+                                      float* y, float* saved, void* stream) {
+    if (!weights_ok(w) || layer < 0 || layer > 1024 || !(p_drop >= 0.f && p_drop < 1.f) || !(eps >= 0.f)) return DR4SR_E_ARG;
+    const int rc = lop::shape_check(B, L, D, H, F);
+    if (rc) return rc;
+    if (B == 0) return 0;                                      // (an empty tensor's pointer may be null)
+    if (!x || !y) return DR4SR_E_ARG;
+    lop::Args a{};
+    a.x = x; a.key_pad = key_pad; a.causal = causal != 0; a.w = *w; a.B = (int)B; a.L = L; a.eps = eps; a.p = p_drop; a.seed = seed; a.step = step;
+    a.layer = layer; a.y = y; a.saved = saved;
+    hipStream_t st = (hipStream_t)stream;
+    if (D == 64 && F == 128) return lop::launch_fwd<64, 128>(a, st);
+    if (D == 64) return lop::launch_fwd<64, 256>(a, st);
+    return lop::launch_fwd<128, 128>(a, st);
+}
+
+extern "C" int dr4sr_sasrec_layer_bwd(const float* x, const uint8_t* key_pad, int32_t causal, const dr4sr_layer_weights* w, int64_t B, int32_t L,
+                                      int32_t D, int32_t H, int32_t F, float eps, float p_drop, uint64_t seed, uint32_t step, int32_t layer,
+                                      const float* saved, const float* dy, float* dx, const dr4sr_layer_grads* dw, void* ws, int64_t ws_bytes,
+                                      void* stream) {
+    if (!weights_ok(w) || !grads_ok(dw) || layer < 0 || layer > 1024 || !(p_drop >= 0.f && p_drop < 1.f) || !(eps >= 0.f)) return DR4SR_E_ARG;
+    const int rc = lop::shape_check(B, L, D, H, F);
+    if (rc) return rc;
+    if (B > 0 && (!x || !saved || !dy || !dx)) return DR4SR_E_ARG;
+    if (B > 0 && (!ws || ws_bytes < (int64_t)lop::n_slots(B) * lop::slot_floats(D, F) * (int64_t)sizeof(float))) return DR4SR_E_WS;
+    hipStream_t st = (hipStream_t)stream;
+    if (B == 0) {                                              // no sequence: the gradients of the weights are zeros
+        const dr4sr_layer_grads& g = *dw;
+        float* t[12] = {g.in_proj_weight, g.in_proj_bias, g.out_proj_weight, g.out_proj_bias, g.linear1_weight, g.linear1_bias,
+                        g.linear2_weight, g.linear2_bias, g.norm1_weight, g.norm1_bias, g.norm2_weight, g.norm2_bias};
+        const int64_t n[12] = {3LL * D * D, 3LL * D, (int64_t)D * D, D, (int64_t)F * D, F, (int64_t)D * F, D, D, D, D, D};
+        for (int i = 0; i < 12; ++i) {
+            const int e = hip_ret(hipMemsetAsync(t[i], 0, n[i] * sizeof(float), st));
+            if (e) return e;
+        }
+        return 0;
+    }
+    lop::Args a{};
+    a.x = x; a.key_pad = key_pad; a.causal = causal != 0; a.w = *w; a.B = (int)B; a.L = L; a.eps = eps; a.p = p_drop; a.seed = seed; a.step = step;
+    a.layer = layer; a.saved = const_cast<float*>(saved); a.dy = dy; a.dx = dx; a.ws = (float*)ws;
+    if (D == 64 && F == 128) return lop::launch_bwd<64, 128>(a, *dw, st);
+    if (D == 64) return lop::launch_bwd<64, 256>(a, *dw, st);
+    return lop::launch_bwd<128, 128>(a, *dw, st);
+}
+
+static int pool_check(const void* a, const void* b, const void* c, int64_t B, int32_t L, int32_t D, int32_t pooling) {
+    if (!a || !b || !c || B < 0 || L < 1 || D < 1) return DR4SR_E_ARG;
+    if (pooling != DR4SR_POOL_ORIGIN && pooling != DR4SR_POOL_LAST && pooling != DR4SR_POOL_MEAN) return DR4SR_E_ARG;
+    return 0;
+}
+static unsigned pool_blocks(int64_t n) {
+    const int64_t b = (n + 255) / 256;
+    return (unsigned)(b > 4096 ? 4096 : b);
+}
+
+extern "C" int dr4sr_seq_pool_fwd(const float* x, const int64_t* seqlen, int32_t pooling, int64_t B, int32_t L, int32_t D, float* out, void* stream) {
+    const int rc = pool_check(x, seqlen, out, B, L, D, pooling);
+    if (rc) return rc;
+    if (B == 0) return 0;
+    const int64_t n = pooling == DR4SR_POOL_ORIGIN ? B * L * D : B * D;
+    hipLaunchKernelGGL(lop::k_pool_fwd, dim3(pool_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, seqlen, pooling, B, L, D, out);
+    return DR4SR_LAUNCH_CHECK();
+}
+
+extern "C" int dr4sr_dropout_apply(const float* x, int64_t n, float p_drop, uint64_t seed, uint32_t step, uint32_t site, float* out, void* stream) {
+    if (!x || !out || n < 0 || (n & 3) || !(p_drop >= 0.f && p_drop < 1.f)) return DR4SR_E_ARG;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(lop::k_dropout_apply, dim3(pool_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, x, n / 4, p_drop, seed, step, site, out);
+    return DR4SR_LAUNCH_CHECK();
+}
+
+extern "C" int dr4sr_embed_gather_posadd_bwd(const float* dx, const int64_t* idx, int64_t B, int32_t L, int32_t D, int32_t n_items, int32_t n_pos,
+                                             float* dE, float* dP, void* stream) {
+    if (!dx || !idx || !dE || !dP || B < 0 || L < 1 || n_items < 1 || n_pos < L || B > (1 << 24)) return DR4SR_E_ARG;
+    if (D < 4 || (D & 3)) return DR4SR_E_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    int e = hip_ret(hipMemsetAsync(dE, 0, (size_t)n_items * D * sizeof(float), st));
+    if (!e) e = hip_ret(hipMemsetAsync(dP, 0, (size_t)n_pos * D * sizeof(float), st));
+    if (e || B == 0) return e;
+    hipLaunchKernelGGL(lop::k_embed_bwd_table, dim3(pool_blocks(B * L * (D / 4))), dim3(256), 0, st, dx, idx, B * L, D, n_items, dE);
+    hipLaunchKernelGGL(lop::k_embed_bwd_pos, dim3((L * D + 255) / 256), dim3(256), 0, st, dx, (int)B, L * D, dP);
+    return DR4SR_LAUNCH_CHECK();
+}
+
+extern "C" int dr4sr_seq_pool_bwd(const float* dout, const int64_t* seqlen, int32_t pooling, int64_t B, int32_t L, int32_t D, float* dx, void* stream) {
+    const int rc = pool_check(dout, seqlen, dx, B, L, D, pooling);
+    if (rc) return rc;
+    if (B == 0) return 0;
+    hipLaunchKernelGGL(lop::k_pool_bwd, dim3(pool_blocks(B * L * D)), dim3(256), 0, (hipStream_t)stream, dout, seqlen, pooling, B, L, D, dx);
+    return DR4SR_LAUNCH_CHECK();
+}

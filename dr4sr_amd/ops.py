@@ -14,14 +14,22 @@ a reference-style model written against plain torch ops:
     full_score_topk(q, E, hist, item_blocked, k) -> (score, ids)   model/basemodel.py:354-365
     target_rank(q, E, target, hist, item_blocked) -> rank int32 [B]   the target's position in that top-k order, without the top-k
     fused_adam_(params, grads, m, v, state, lr, b1, b2, eps, wd)   torch.optim.Adam on flat buffers (in place)
+    sasrec_layer(x, key_padding_mask?, causal, <12 layer tensors>, n_head, eps, p_drop, seed, step, layer) -> (y, saved)
+                                                              one TransformerEncoderLayer of model/sasrec.py:21-30,:68 on dense [B, L, D]
+                                                              (autograd: d x and the 12 weight gradients, bit-reproducible)
+    seq_pool(x, seqlen, pooling) -> out                       module/layers.py:41-73 'origin' | 'last', module/functional.py:50-55 'mean'
+    dropout(x, p_drop, seed, step, site) -> out               model/sasrec.py:66 with the library's Philox masks (DR4SR_SITE_EMB)
+    (+ embed_gather_posadd_backward, sasrec_layer_backward, seq_pool_backward: the autograd formulas, ops themselves)
 
 Every implementation only enqueues HIP kernels of libdr4sr_hip.so on the current stream; there is no CPU kernel (the ops raise on
-CPU tensors).  The plan-based entry points (whole fused training steps, encoders with their workspaces) are driven by the engines
-(dr4sr_amd/engine.py ...) and are deliberately not dispatcher ops: they own device state (workspace, RNG step, Adam step).
+CPU tensors).  The encoder LAYER is a dispatcher op: stateless, dense tensors in and out, its dropout keyed by explicit (seed, step,
+layer) arguments — dr4sr_amd/module/layers.py SASRecQueryEncoderOps is the reference's query encoder written on these ops.  What stays
+outside the dispatcher are the plan-based entry points (whole fused training steps, the packed encoders with their workspaces), driven by
+the engines (dr4sr_amd/engine.py ...): they own device state (workspace, RNG step, Adam step).
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import os
 
@@ -60,6 +68,39 @@ def embed_gather_posadd(E: torch.Tensor, P: torch.Tensor, idx: torch.Tensor) -> 
 @embed_gather_posadd.register_fake
 def _(E, P, idx):
     return E.new_empty(idx.shape[0], idx.shape[1], E.shape[1])
+
+
+@torch.library.custom_op(f"{NS}::embed_gather_posadd_backward", mutates_args=())
+def embed_gather_posadd_backward(g_x: torch.Tensor, idx: torch.Tensor, n_items: int, n_pos: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (dE [n_items, D], dP [n_pos, D]); the PAD row of dE is exactly 0 (nn.Embedding(padding_idx=0), model/basemodel.py:42)"""
+    _need_cuda(g_x, idx)
+    lib = _lib.load()
+    B, L, D = (int(s) for s in g_x.shape)
+    g, ic = g_x.contiguous().float(), idx.contiguous()
+    dE = torch.empty(n_items, D, dtype=torch.float32, device=g.device)
+    dP = torch.empty(n_pos, D, dtype=torch.float32, device=g.device)
+    _lib.check(lib.dr4sr_embed_gather_posadd_bwd(_lib.ptr(g), _lib.ptr(ic), B, L, D, n_items, n_pos, _lib.ptr(dE), _lib.ptr(dP),
+                                                 _lib.cur_stream()), "dr4sr_embed_gather_posadd_bwd")
+    return dE, dP
+
+
+@embed_gather_posadd_backward.register_fake
+def _(g_x, idx, n_items, n_pos):
+    return g_x.new_empty(n_items, g_x.shape[2]), g_x.new_empty(n_pos, g_x.shape[2])
+
+
+def _egp_setup(ctx, inputs, output):
+    E, P, idx = inputs
+    ctx.n_items, ctx.n_pos = E.shape[0], P.shape[0]
+    ctx.save_for_backward(idx)
+
+
+def _egp_backward(ctx, g):
+    dE, dP = embed_gather_posadd_backward(g, ctx.saved_tensors[0], ctx.n_items, ctx.n_pos)
+    return dE, dP, None
+
+
+embed_gather_posadd.register_autograd(_egp_backward, setup_context=_egp_setup)
 
 
 # ------------------------------------------------------------------------------------------------ scorer + loss
@@ -253,5 +294,192 @@ def fused_adam_(params: torch.Tensor, grads: torch.Tensor, adam_m: torch.Tensor,
                                    lr, beta1, beta2, eps, weight_decay, _lib.cur_stream()), "dr4sr_adam_flat")
 
 
+# ------------------------------------------------------------------------------------------------ encoder layer / pooling / dropout
+def _layer_dims(x, in_proj_weight, linear1_weight, n_head):
+    if x.dim() != 3 or x.dtype != torch.float32:
+        raise _lib.Dr4srError("sasrec_layer: x must be a [B, L, D] float32 tensor")
+    B, L, D = (int(s) for s in x.shape)
+    return B, L, D, int(n_head), int(linear1_weight.shape[0])
+
+
+def _saved_floats(B, L, D, F):
+    return B * ((L * (6 * D + F) + 2 * L * L + 3) // 4 * 4)           # dr4sr_sasrec_layer_saved_floats for a supported shape
+
+
+def _mask_u8(m):
+    if m is None:
+        return None
+    m = m.contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)
+
+
+def _layer_struct(cls, tensors):
+    return cls(*[_lib.ptr(t) for t in tensors])
+
+
+@torch.library.custom_op(f"{NS}::sasrec_layer", mutates_args=())
+def sasrec_layer(x: torch.Tensor, key_padding_mask: Optional[torch.Tensor], causal: bool, in_proj_weight: torch.Tensor,
+                 in_proj_bias: torch.Tensor, out_proj_weight: torch.Tensor, out_proj_bias: torch.Tensor, linear1_weight: torch.Tensor,
+                 linear1_bias: torch.Tensor, linear2_weight: torch.Tensor, linear2_bias: torch.Tensor, norm1_weight: torch.Tensor,
+                 norm1_bias: torch.Tensor, norm2_weight: torch.Tensor, norm2_bias: torch.Tensor, n_head: int, eps: float, p_drop: float,
+                 seed: int, step: int, layer: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """one post-norm TransformerEncoderLayer (model/sasrec.py:21-30) on x [B, L, D]; key_padding_mask [B, L] (True / non-zero: padded)
+    or None, causal adds triu(1); a query with no admissible key gets a zero attention context (include/dr4sr_hip.h).  `saved` is the
+    opaque buffer the backward reads"""
+    ws_ = (in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, linear1_weight, linear1_bias, linear2_weight, linear2_bias,
+           norm1_weight, norm1_bias, norm2_weight, norm2_bias)
+    _need_cuda(x, key_padding_mask, *ws_)
+    lib = _lib.load()
+    B, L, D, H, F = _layer_dims(x, in_proj_weight, linear1_weight, n_head)
+    n = int(lib.dr4sr_sasrec_layer_saved_floats(B, L, D, H, F))
+    _lib.check(min(n, 0), "dr4sr_sasrec_layer_saved_floats")
+    xc, kp = x.contiguous(), _mask_u8(key_padding_mask)
+    wc = [t.contiguous() for t in ws_]
+    y = torch.empty_like(xc)
+    saved = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
+    w = _layer_struct(_lib.LayerWeights, wc)
+    _lib.check(lib.dr4sr_sasrec_layer_fwd(_lib.ptr(xc), _lib.ptr(kp), int(causal), w, B, L, D, H, F, eps, p_drop, seed & 0xFFFFFFFFFFFFFFFF,
+                                          step & 0xFFFFFFFF, layer, _lib.ptr(y), _lib.ptr(saved), _lib.cur_stream()), "dr4sr_sasrec_layer_fwd")
+    return y, saved
+
+
+@sasrec_layer.register_fake
+def _(x, key_padding_mask, causal, in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, linear1_weight, linear1_bias, linear2_weight,
+      linear2_bias, norm1_weight, norm1_bias, norm2_weight, norm2_bias, n_head, eps, p_drop, seed, step, layer):
+    B, L, D = x.shape
+    return torch.empty_like(x), x.new_empty(max(_saved_floats(B, L, D, linear1_weight.shape[0]), 1))
+
+
+@torch.library.custom_op(f"{NS}::sasrec_layer_backward", mutates_args=())
+def sasrec_layer_backward(x: torch.Tensor, key_padding_mask: Optional[torch.Tensor], causal: bool, in_proj_weight: torch.Tensor,
+                          in_proj_bias: torch.Tensor, out_proj_weight: torch.Tensor, out_proj_bias: torch.Tensor,
+                          linear1_weight: torch.Tensor, linear1_bias: torch.Tensor, linear2_weight: torch.Tensor, linear2_bias: torch.Tensor,
+                          norm1_weight: torch.Tensor, norm1_bias: torch.Tensor, norm2_weight: torch.Tensor, norm2_bias: torch.Tensor,
+                          n_head: int, eps: float, p_drop: float, seed: int, step: int, layer: int, saved: torch.Tensor,
+                          dy: torch.Tensor) -> List[torch.Tensor]:
+    """-> [dx, the 12 weight gradients in the argument order]; written, not accumulated; bit-reproducible"""
+    ws_ = (in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, linear1_weight, linear1_bias, linear2_weight, linear2_bias,
+           norm1_weight, norm1_bias, norm2_weight, norm2_bias)
+    _need_cuda(x, key_padding_mask, saved, dy, *ws_)
+    lib = _lib.load()
+    B, L, D, H, F = _layer_dims(x, in_proj_weight, linear1_weight, n_head)
+    nb = int(lib.dr4sr_sasrec_layer_workspace_bytes(B, L, D, H, F))
+    _lib.check(min(nb, 0), "dr4sr_sasrec_layer_workspace_bytes")
+    xc, kp, dyc, sc = x.contiguous(), _mask_u8(key_padding_mask), dy.contiguous().float(), saved.contiguous()
+    wc = [t.contiguous() for t in ws_]
+    dx = torch.empty_like(xc)
+    dws = [torch.empty_like(t) for t in wc]
+    ws = torch.empty(max(nb // 4, 1), dtype=torch.float32, device=x.device)
+    w, g = _layer_struct(_lib.LayerWeights, wc), _layer_struct(_lib.LayerGrads, dws)
+    _lib.check(lib.dr4sr_sasrec_layer_bwd(_lib.ptr(xc), _lib.ptr(kp), int(causal), w, B, L, D, H, F, eps, p_drop, seed & 0xFFFFFFFFFFFFFFFF,
+                                          step & 0xFFFFFFFF, layer, _lib.ptr(sc), _lib.ptr(dyc), _lib.ptr(dx), g, _lib.ptr(ws), nb,
+                                          _lib.cur_stream()), "dr4sr_sasrec_layer_bwd")
+    return [dx] + dws
+
+
+@sasrec_layer_backward.register_fake
+def _(x, key_padding_mask, causal, in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, linear1_weight, linear1_bias, linear2_weight,
+      linear2_bias, norm1_weight, norm1_bias, norm2_weight, norm2_bias, n_head, eps, p_drop, seed, step, layer, saved, dy):
+    return [torch.empty_like(t) for t in (x, in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, linear1_weight, linear1_bias,
+                                          linear2_weight, linear2_bias, norm1_weight, norm1_bias, norm2_weight, norm2_bias)]
+
+
+def _layer_setup(ctx, inputs, output):
+    ctx.rest = inputs[1:3] + inputs[15:]                    # mask, causal, n_head, eps, p_drop, seed, step, layer
+    ctx.save_for_backward(inputs[0], *inputs[3:15], output[1])
+    ctx.mark_non_differentiable(output[1])
+
+
+def _layer_backward(ctx, g_y, g_saved):
+    x, *w, saved = ctx.saved_tensors
+    mask, causal = ctx.rest[:2]
+    out = sasrec_layer_backward(x, mask, causal, *w, *ctx.rest[2:], saved, g_y)
+    return (out[0], None, None, *out[1:], None, None, None, None, None, None)
+
+
+sasrec_layer.register_autograd(_layer_backward, setup_context=_layer_setup)
+
+
+def _pool_shape(x, pooling):
+    return x.shape if pooling == _lib.POOL_ORIGIN else (x.shape[0], x.shape[2])
+
+
+@torch.library.custom_op(f"{NS}::seq_pool", mutates_args=())
+def seq_pool(x: torch.Tensor, seqlen: torch.Tensor, pooling: int) -> torch.Tensor:
+    """SeqPoolingLayer on x [B, L, D]: pooling = POOL_ORIGIN (1, zero rows >= seqlen -> [B, L, D]), POOL_LAST (2, row seqlen - 1 -> [B, D])
+    or POOL_MEAN (3, mean of the rows < seqlen -> [B, D]); a row with seqlen 0 pools to zeros"""
+    _need_cuda(x, seqlen)
+    lib = _lib.load()
+    B, L, D = (int(s) for s in x.shape)
+    xc, sl = x.contiguous().float(), seqlen.contiguous().view(-1).to(torch.int64)
+    out = torch.empty(_pool_shape(xc, pooling), dtype=torch.float32, device=x.device)
+    _lib.check(lib.dr4sr_seq_pool_fwd(_lib.ptr(xc), _lib.ptr(sl), pooling, B, L, D, _lib.ptr(out), _lib.cur_stream()), "dr4sr_seq_pool_fwd")
+    return out
+
+
+@seq_pool.register_fake
+def _(x, seqlen, pooling):
+    return x.new_empty(_pool_shape(x, pooling))
+
+
+@torch.library.custom_op(f"{NS}::seq_pool_backward", mutates_args=())
+def seq_pool_backward(g_out: torch.Tensor, seqlen: torch.Tensor, pooling: int, L: int) -> torch.Tensor:
+    _need_cuda(g_out, seqlen)
+    lib = _lib.load()
+    B, D = int(g_out.shape[0]), int(g_out.shape[-1])
+    g, sl = g_out.contiguous().float(), seqlen.contiguous().view(-1).to(torch.int64)
+    dx = torch.empty(B, L, D, dtype=torch.float32, device=g.device)
+    _lib.check(lib.dr4sr_seq_pool_bwd(_lib.ptr(g), _lib.ptr(sl), pooling, B, L, D, _lib.ptr(dx), _lib.cur_stream()), "dr4sr_seq_pool_bwd")
+    return dx
+
+
+@seq_pool_backward.register_fake
+def _(g_out, seqlen, pooling, L):
+    return g_out.new_empty(g_out.shape[0], L, g_out.shape[-1])
+
+
+def _pool_setup(ctx, inputs, output):
+    x, seqlen, pooling = inputs
+    ctx.pooling, ctx.L = pooling, x.shape[1]
+    ctx.save_for_backward(seqlen)
+
+
+def _pool_backward(ctx, g):
+    return seq_pool_backward(g, ctx.saved_tensors[0], ctx.pooling, ctx.L), None, None
+
+
+seq_pool.register_autograd(_pool_backward, setup_context=_pool_setup)
+
+
+@torch.library.custom_op(f"{NS}::dropout", mutates_args=())
+def dropout(x: torch.Tensor, p_drop: float, seed: int, step: int, site: int) -> torch.Tensor:
+    """x * keep / (1 - p) with the library's Philox decisions of stream (seed, step, site), element order = x's memory order (the embedding
+    dropout of a model written on the ops: site SITE_EMB); numel a multiple of 4.  Its backward is the same op on the gradient"""
+    _need_cuda(x)
+    lib = _lib.load()
+    xc = x.contiguous().float()
+    out = torch.empty_like(xc)
+    _lib.check(lib.dr4sr_dropout_apply(_lib.ptr(xc), xc.numel(), p_drop, seed & 0xFFFFFFFFFFFFFFFF, step & 0xFFFFFFFF, site, _lib.ptr(out),
+                                       _lib.cur_stream()), "dr4sr_dropout_apply")
+    return out
+
+
+@dropout.register_fake
+def _(x, p_drop, seed, step, site):
+    return torch.empty_like(x)
+
+
+def _drop_setup(ctx, inputs, output):
+    ctx.rest = inputs[1:]
+
+
+def _drop_backward(ctx, g):
+    return dropout(g, *ctx.rest), None, None, None, None
+
+
+dropout.register_autograd(_drop_backward, setup_context=_drop_setup)
+
+
 OPS = ("embed_gather_posadd", "score_bce", "score_bce_backward", "score_bpr", "score_bpr_backward", "loss_from_scores",
-       "loss_from_scores_backward", "neg_sample", "full_score_topk", "target_rank", "fused_adam_")
+       "loss_from_scores_backward", "neg_sample", "full_score_topk", "target_rank", "fused_adam_",
+       "sasrec_layer", "sasrec_layer_backward", "seq_pool", "seq_pool_backward", "dropout", "embed_gather_posadd_backward")

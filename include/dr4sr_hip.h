@@ -901,6 +901,62 @@ int64_t dr4sr_gnn_workspace_bytes(int32_t n_items, int32_t D, int64_t nnz);
 int dr4sr_gnn_propagate(const int64_t* row_ptr, const int32_t* col, const float* val, int32_t n_items, int32_t D, int32_t n_hop,
                         const float* in, float* out, int32_t accumulate, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- additive to ABI 10: the stateless encoder-layer op and sequence pooling on dense tensors (csrc/layer_op.hip; what
+ * torch.ops.dr4sr_hip.sasrec_layer / seq_pool / dropout run).  No plan, no workspace that survives a call, no device state words.
+ *
+ * The layer is ONE post-norm torch.nn.TransformerEncoderLayer as the reference configures it (model/sasrec.py:21-30): packed in_proj,
+ * score scale 1 / sqrt(head_dim), exact-erf GELU, LayerNorm eps from the caller; x, y, dy, dx are [B, L, D] fp32, contiguous.  The mask is
+ * general: key_pad is [B, L] uint8 (non-zero: the key is padded) or NULL for no padded key, and causal != 0 adds triu(1) (query i admits
+ * keys j <= i).  A QUERY POSITION WITH NO ADMISSIBLE KEY GETS A ZERO ATTENTION CONTEXT (torch yields NaN there; the reference never reads
+ * such a position): its output row is LayerNorm of the remaining terms, and the result and every gradient stay finite.
+ * Supported shapes (anything else: DR4SR_E_SHAPE, before any launch): L <= 64 and (D, F, head_dim) in (64, 128 | 256, 32), (128, 128, 64),
+ * head_dim = D / H.  DR4SR_E_ARG: a null pointer (key_pad and, in the forward, saved may be NULL), B < 0, p_drop outside [0, 1), eps < 0,
+ * layer outside [0, 1024].  B = 0 launches nothing (the backward zero-fills dw); the activation pointers may then be null.
+ *
+ * Dropout: the four sites DR4SR_SITE_ATTN / PROJ / ACT / FFN + 4 * layer of the library's Philox stream keyed by (seed, step, site); the
+ * decision of an element is that of element e of the hooks header's dr4sr_dropout_mask for the same (p, seed, step, site), with
+ *     PROJ, FFN:  e = (b * L + pos) * D + c          ACT:  e = (b * L + pos) * F + c          ATTN:  e = ((b * H + h) * L + i) * L + j
+ * (i the query, j the key).  p_drop == 0 does no RNG work.
+ *
+ * saved (forward: written when non-NULL; backward: read) is opaque, dr4sr_sasrec_layer_saved_floats floats: NULL for inference.  The
+ * backward takes the inputs of the forward it differentiates; dx and the 12 tensors of dw are WRITTEN, not accumulated.  It uses no float
+ * atomics: every workgroup sums the sequences it owns in index order into its slot of ws (dr4sr_sasrec_layer_workspace_bytes), a second
+ * launch adds the slots in index order — two calls give the same bits.  A null or too small ws: DR4SR_E_WS.
+ * Launches on `stream` only (capturable), no allocation, no host synchronisation. */
+typedef struct dr4sr_layer_weights {       /* the layer tensors in the flat layout's order */
+    const float *in_proj_weight, *in_proj_bias, *out_proj_weight, *out_proj_bias, *linear1_weight, *linear1_bias, *linear2_weight,
+        *linear2_bias, *norm1_weight, *norm1_bias, *norm2_weight, *norm2_bias;
+} dr4sr_layer_weights;
+typedef struct dr4sr_layer_grads {
+    float *in_proj_weight, *in_proj_bias, *out_proj_weight, *out_proj_bias, *linear1_weight, *linear1_bias, *linear2_weight, *linear2_bias,
+        *norm1_weight, *norm1_bias, *norm2_weight, *norm2_bias;
+} dr4sr_layer_grads;
+/* floats / bytes, or a negative DR4SR_E_* code */
+int64_t dr4sr_sasrec_layer_saved_floats(int64_t B, int32_t L, int32_t D, int32_t H, int32_t F);
+int64_t dr4sr_sasrec_layer_workspace_bytes(int64_t B, int32_t L, int32_t D, int32_t H, int32_t F);
+int dr4sr_sasrec_layer_fwd(const float* x, const uint8_t* key_pad, int32_t causal, const dr4sr_layer_weights* w, int64_t B, int32_t L,
+                           int32_t D, int32_t H, int32_t F, float eps, float p_drop, uint64_t seed, uint32_t step, int32_t layer, float* y,
+                           float* saved, void* stream);
+int dr4sr_sasrec_layer_bwd(const float* x, const uint8_t* key_pad, int32_t causal, const dr4sr_layer_weights* w, int64_t B, int32_t L,
+                           int32_t D, int32_t H, int32_t F, float eps, float p_drop, uint64_t seed, uint32_t step, int32_t layer,
+                           const float* saved, const float* dy, float* dx, const dr4sr_layer_grads* dw, void* ws, int64_t ws_bytes,
+                           void* stream);
+/* Pooling of x [B, L, D] by seqlen [B] int64 (clamped to [0, L]): DR4SR_POOL_ORIGIN zeroes the rows at pos >= seqlen -> [B, L, D]
+ * (module/layers.py:41-50); DR4SR_POOL_LAST is row seqlen - 1 -> [B, D] (layers.py:69-73); DR4SR_POOL_MEAN the mean of the rows below
+ * seqlen -> [B, D] (module/functional.py:50-55).  A row with seqlen 0 pools to zeros.  The backward WRITES dx [B, L, D] from dout in the
+ * forward's output shape.  Any other pooling value, a null pointer, B < 0, L < 1, D < 1: DR4SR_E_ARG. */
+int dr4sr_seq_pool_fwd(const float* x, const int64_t* seqlen, int32_t pooling, int64_t B, int32_t L, int32_t D, float* out, void* stream);
+int dr4sr_seq_pool_bwd(const float* dout, const int64_t* seqlen, int32_t pooling, int64_t B, int32_t L, int32_t D, float* dx, void* stream);
+/* out[e] = x[e] * keep(e) / (1 - p) with the keep decision of element e of stream (seed, step, site), n a multiple of 4 (the embedding
+ * dropout, DR4SR_SITE_EMB, of a model written on the ops; its own backward with dy for x).  out may be x.  p_drop == 0 copies. */
+int dr4sr_dropout_apply(const float* x, int64_t n, float p_drop, uint64_t seed, uint32_t step, uint32_t site, float* out, void* stream);
+/* Backward of dr4sr_embed_gather_posadd for a model written on the ops: dE [n_items, D] and dP [n_pos, D] are WRITTEN — dE[idx] += dx over
+ * the tokens (PAD id 0 and ids outside the table pass nothing: row 0 is exactly 0), dP[pos] = the sum of dx[b, pos] over b in index order
+ * (rows at and behind L are 0).  The table scatter adds with float atomics: dE is reproducible to rounding, not to the bit.  D a multiple
+ * of 4 (else DR4SR_E_SHAPE); a null pointer, B < 0 or above 2^24, L < 1, n_items < 1, n_pos < L: DR4SR_E_ARG. */
+int dr4sr_embed_gather_posadd_bwd(const float* dx, const int64_t* idx, int64_t B, int32_t L, int32_t D, int32_t n_items, int32_t n_pos,
+                                  float* dE, float* dP, void* stream);
+
 /* Test / measurement hooks (dr4sr_dropout_mask, dr4sr_*_launch_kernel) are NOT part of this product surface: they are declared in
  * include/dr4sr_hip_hooks.h, and nothing under dr4sr_amd/ calls them. */
 
