@@ -268,6 +268,33 @@ __device__ __forceinline__ uint32_t lane_xor1_u32_ref(uint32_t v) { return (uint
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
+// Write-through (sc1) stores for bytes that only a LATER launch reads: the line leaves the XCD's L2 while the kernel still runs, instead of
+// staying dirty until the end-of-kernel write-back (the eight L2s are not coherent, so every launch ends by draining what it dirtied).
+// 16 bytes go through the raw-buffer builtin with aux = 16 (sc1): the compiler's wait-count pass sees the store like any other.  A WtBuf
+// covers exactly ONE destination array (num_records = its bytes), so an offset past its end is dropped by the hardware's range check and
+// can not land in a neighbouring array.  Byte offsets are 32-bit: a site takes this form only where its array is under 2 GiB — chosen by
+// the HOST's instantiation, never by a branch in the kernel.  -DDR4SR_NO_WT_STORES: kWtStores = false, every site compiles to its plain
+// store again (A / B builds).
+#ifdef DR4SR_NO_WT_STORES
+constexpr bool kWtStores = false;
+#else
+constexpr bool kWtStores = true;
+#endif
+constexpr int64_t kWtMaxBytes = (int64_t)1 << 31;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+struct WtBuf { __amdgpu_buffer_rsrc_t r; };
+__device__ __forceinline__ WtBuf wt_buf(float* base, int64_t bytes) {      // word 3 = 0x00020000: raw buffer, 32-bit data format (gfx9)
+    return WtBuf{__builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000)};
+}
+__device__ __forceinline__ void st4_wt(WtBuf b, uint32_t byte_off, float4 v) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{v.x, v.y, v.z, v.w}), b.r, (int)byte_off, 0, 16);
+}
+// st4 at float index `idx` of the array `base`: write-through through `b` (which covers `base`) or the plain store
+template <bool WT>
+__device__ __forceinline__ void st4_sel(WtBuf b, float* base, int64_t idx, float4 v) {
+    if constexpr (WT) st4_wt(b, (uint32_t)idx * 4u, v); else st4(base + idx, v);
+}
+
 // erf by Abramowitz-Stegun 7.1.26 (|abs error| <= 1.5e-7, i.e. fp32-rounding class) on v_rcp/v_exp: ~15 VALU instead of
 // libm erff's ~60 — the GELU row passes are VALU-latency-bound with one wave per SIMD.
 __device__ __forceinline__ float erf_fast(float x) {

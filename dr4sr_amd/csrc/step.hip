@@ -330,7 +330,9 @@ static int get_ws(const dr4sr_sasrec_plan* p, Workspace* ws) {
 // from (t, lr, b1, b2) is ignored and the thread evaluates the expressions itself.  Every other launch (the eager dr4sr_adam_step, the last
 // step of a graph, the flat entry point without a prep, the other optimizers) is the BC = false form: corrections inline, as before.
 struct AdamNext { int enable; int phase2_launch; PrepArgs prep; };
-template <int OPT, bool BC = false>
+// WT (host: kWtStores and every array under 2 GiB): the sweep's stores of P, M, V and of the zeroed G are write-through (common.h st4_wt) —
+// the next launch reads them and nothing in this one does, so they drain beside the sweep and not at the end of the kernel.
+template <int OPT, bool BC = false, bool WT = false>
 __global__ __launch_bounds__(256) void k_adam(float* __restrict__ P, float* __restrict__ G, float* __restrict__ M,
                                               float* __restrict__ V, int64_t n, int* __restrict__ state, float lr, float b1,
                                               float b2, float eps, float wd, float* __restrict__ loss_log,
@@ -380,6 +382,8 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ P, float* __re
         }
         if (!next.enable && loss_log && blk == 0 && threadIdx.x == 0) loss_log[log_index ? max(*log_index - 1, 0) : 0] = G[n + 1] * gs;
         const int64_t n4 = n / 4;
+        // (the second moment's fused multiply-add is written out: left to the compiler, `ve * b2 + (1 - b2) g g` contracted differently beside
+        // the write-through stores than beside the plain ones — other low bits; fmaf(ve, b2, .) is what the plain form has always compiled to)
         auto upd = [&](float& pe, float& me, float& ve, float ge) {
             const float g = ge * gs + wd * pe;
             if constexpr (OPT == DR4SR_OPT_SGD) {
@@ -388,11 +392,11 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ P, float* __re
                 ve = ve + g * g;
                 pe = pe - lr * (g / (sqrtf(ve) + eps));
             } else if constexpr (OPT == DR4SR_OPT_RMSPROP) {
-                ve = ve * b2 + (1.0f - b2) * g * g;
+                ve = fmaf(ve, b2, (1.0f - b2) * g * g);
                 pe = pe - lr * (g / (sqrtf(ve) + eps));
             } else {
                 me = me + (g - me) * (1.0f - b1);
-                ve = ve * b2 + (1.0f - b2) * g * g;
+                ve = fmaf(ve, b2, (1.0f - b2) * g * g);
                 const float denom = sqrtf(ve) * inv_sqrt_bc2 + eps;
                 pe = pe - step_size * (me / denom);
             }
@@ -402,11 +406,12 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ P, float* __re
         // bandwidth-bound at 3 iterations per thread)
         const int64_t stride = (int64_t)nblk * 256;
         const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        const WtBuf bP = wt_buf(P, n * 4), bM = wt_buf(M, n * 4), bV = wt_buf(V, n * 4), bG = wt_buf(G, n * 4);     // (unused where !WT)
         for (int64_t i = (int64_t)blk * 256 + threadIdx.x; i < n4; i += 2 * stride) {
             const int64_t j = i + stride;
             const bool two = j < n4;
             if (poisoned) {                                // skipped step: only the next step's zeroed gradient is still owed
-                if (next.enable) { st4(G + 4 * i, z4); if (two) st4(G + 4 * j, z4); }
+                if (next.enable) { st4_sel<WT>(bG, G, 4 * i, z4); if (two) st4_sel<WT>(bG, G, 4 * j, z4); }
                 continue;
             }
             float4 p0 = ld4(P + 4 * i), m0 = useM ? ld4(M + 4 * i) : z4, v0 = useV ? ld4(V + 4 * i) : z4;
@@ -414,12 +419,12 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ P, float* __re
             float4 p1 = p0, m1 = m0, v1 = v0, g1 = g0;
             if (two) { p1 = ld4(P + 4 * j); if (useM) m1 = ld4(M + 4 * j); if (useV) v1 = ld4(V + 4 * j); g1 = ld4(G + 4 * j); }
             upd(p0.x, m0.x, v0.x, g0.x); upd(p0.y, m0.y, v0.y, g0.y); upd(p0.z, m0.z, v0.z, g0.z); upd(p0.w, m0.w, v0.w, g0.w);
-            st4(P + 4 * i, p0); if (useM) st4(M + 4 * i, m0); if (useV) st4(V + 4 * i, v0);
-            if (next.enable) st4(G + 4 * i, z4);
+            st4_sel<WT>(bP, P, 4 * i, p0); if (useM) st4_sel<WT>(bM, M, 4 * i, m0); if (useV) st4_sel<WT>(bV, V, 4 * i, v0);
+            if (next.enable) st4_sel<WT>(bG, G, 4 * i, z4);
             if (two) {
                 upd(p1.x, m1.x, v1.x, g1.x); upd(p1.y, m1.y, v1.y, g1.y); upd(p1.z, m1.z, v1.z, g1.z); upd(p1.w, m1.w, v1.w, g1.w);
-                st4(P + 4 * j, p1); if (useM) st4(M + 4 * j, m1); if (useV) st4(V + 4 * j, v1);
-                if (next.enable) st4(G + 4 * j, z4);
+                st4_sel<WT>(bP, P, 4 * j, p1); if (useM) st4_sel<WT>(bM, M, 4 * j, m1); if (useV) st4_sel<WT>(bV, V, 4 * j, v1);
+                if (next.enable) st4_sel<WT>(bG, G, 4 * j, z4);
             }
         }
     }
@@ -473,15 +478,20 @@ int launch_adam_flat(float* P, float* G, float* M, float* V, int64_t n, int* sta
     const bool p2_inline = DR4SR_ENV("DR4SR_PREP2_INLINE") != nullptr;      // cross-check: phase 2 as the tail of the optimizer launch
     nx.phase2_launch = nx.enable == 2 && !p2_inline;
     const dim3 grid((unsigned)blocks + (nx.enable == 1 ? 1 : 0));
-    switch (opt) {
-        case DR4SR_OPT_SGD: hipLaunchKernelGGL(k_adam<DR4SR_OPT_SGD>, grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx); break;
-        case DR4SR_OPT_ADAGRAD: hipLaunchKernelGGL(k_adam<DR4SR_OPT_ADAGRAD>, grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx); break;
-        case DR4SR_OPT_RMSPROP: hipLaunchKernelGGL(k_adam<DR4SR_OPT_RMSPROP>, grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx); break;
-        default:
-            // the form that reads (and whose prep writes) the bias-correction record: where the prep keeps one (SASRec plans; prep_body.h)
-            if (next && next->bc_rec) hipLaunchKernelGGL((k_adam<DR4SR_OPT_ADAM, true>), grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx);
-            else hipLaunchKernelGGL(k_adam<DR4SR_OPT_ADAM>, grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx);
-    }
+    auto launch = [&](auto wt) {
+        constexpr bool WT = decltype(wt)::value;
+        switch (opt) {
+            case DR4SR_OPT_SGD: hipLaunchKernelGGL((k_adam<DR4SR_OPT_SGD, false, WT>), grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx); break;
+            case DR4SR_OPT_ADAGRAD: hipLaunchKernelGGL((k_adam<DR4SR_OPT_ADAGRAD, false, WT>), grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx); break;
+            case DR4SR_OPT_RMSPROP: hipLaunchKernelGGL((k_adam<DR4SR_OPT_RMSPROP, false, WT>), grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx); break;
+            default:
+                // the form that reads (and whose prep writes) the bias-correction record: where the prep keeps one (SASRec plans; prep_body.h)
+                if (next && next->bc_rec) hipLaunchKernelGGL((k_adam<DR4SR_OPT_ADAM, true, WT>), grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx);
+                else hipLaunchKernelGGL((k_adam<DR4SR_OPT_ADAM, false, WT>), grid, dim3(256), 0, s, P, G, M, V, n, state, lr, b1, b2, eps, wd, loss_log, log_index, nx);
+        }
+    };
+    // write-through stores of the sweep: 32-bit byte offsets, so only where every array is under 2 GiB (common.h)
+    if (n * 4 < kWtMaxBytes) launch(std::bool_constant<kWtStores>{}); else launch(std::false_type{});
     if (nx.phase2_launch) {
         const int B = next->B, per = 8 * 256;
         int g2 = (B + per - 1) / per;
