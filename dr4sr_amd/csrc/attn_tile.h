@@ -29,6 +29,13 @@ constexpr int WR = 80;            // window rows: tokens [t0 - 64, t0 + 16)
 constexpr int QR0 = 64;           // window row of the tile's first token
 constexpr int MT = WR / 16;
 
+// (experiments build, DR4SR_ROWADDS_SKIP bit 0 -> TileAttnArgs::on bit 3: the launch is timed without its dK | dV adds — attribution only)
+#ifdef DR4SR_EXPERIMENTS
+#define XSKIP_KV(A_) (((A_).on & 8) != 0)
+#else
+#define XSKIP_KV(A_) false
+#endif
+
 template <int D>
 struct Lds {
     static constexpr int LD = D + 4;
@@ -351,7 +358,9 @@ __device__ __forceinline__ Keep fwd(const PostArgs& P, const int t0, const int T
 // Measured and dropped (same box, ms per step at B = 256): every wave both phases in sequence, key tiles / feature blocks split between
 // the two waves of a head, so that the atomics are in flight during the dQ phase: 0.1090 against 0.1066; the dK | dV rows through a
 // per-wave LDS exchange tile so that an atomic instruction covers ONE row's 64 columns instead of 4-byte pieces of 16 rows: 0.1091 /
-// 0.1080 — the isolated launch liked both (19.2 against 20.1 us), the step did not.
+// 0.1080 — the isolated launch liked both (19.2 against 20.1 us), the step did not.  Its successor with no exchange (the two MFMA
+// operands swapped: a key-major accumulator, 4 rows x 64 dense bytes per add instruction): B = 256 0.0872 against 0.0840 ms, d = 128 0.1840
+// against 0.1791 (NOTEBOOK "Float atomics as 64-byte row segments").
 // DET (deterministic latency form, kernels.h Workspace::det_lat): the rows another tile adds to as well go to this query tile's partial blocks
 // instead (linear.hip det_kv_rows sums them in query-tile order) — a separate instantiation, the default kernels are unchanged.
 template <int D, bool DET = false>
@@ -461,7 +470,7 @@ __device__ __forceinline__ void bwd(const PostArgs& P, const int t0, const int T
                     float* pb = A.kv_part + (((size_t)(t0 >> 4) * MT + jt) * 16 + i16) * 2 * D + h * DH + fb * 16 + 4 * g;
                     st4(pb, make_float4(dk[0], dk[1], dk[2], dk[3]));
                     st4(pb + D, make_float4(dv[0], dv[1], dv[2], dv[3]));
-                } else {
+                } else if (!XSKIP_KV(A)) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { unsafeAtomicAdd(dst + e, dk[e]); unsafeAtomicAdd(dst + D + e, dv[e]); }
                 }

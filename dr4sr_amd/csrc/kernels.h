@@ -172,6 +172,9 @@ struct QkvEmbBwdArgs {
     // input_weight (dr4sr_sasrec_inputs; WGT instantiations only, picked when inw != NULL): with g = dx0 * mask, d_inw[b][pos] = <g, E[id] + P[pos]> is
     // STORED (d_inw != NULL) and g <- inw[b][pos] * g before any consumer of g.  E / P: the forward's tables (set whenever inw is)
     const float* inw; float* d_inw; const float* E; const float* P;
+#ifdef DR4SR_EXPERIMENTS
+    int xskip;                   // DR4SR_ROWADDS_SKIP bit 2: the dE adds are skipped (attribution of the launch's time only)
+#endif
 };
 
 // scorer half of the fused last-layer launch (k_post_mid / k_wt_post_mid)

@@ -804,10 +804,47 @@ __device__ __forceinline__ void ln_bwd_rowpass(const float* __restrict__ Gg, con
 // record instead (gp == NULL: nothing to add) and post_bwd_body issues the adds behind the last load it waits for (the ctx rows of the rd
 // sum); the launch's remaining phase, the in-tile attention backward, reads LDS.  The products are the scorer's own (dpos * wt, dneg * wt
 // times the query float4).  -DDR4SR_ADDS_IN_SCORER builds the adds-in-place form for A / B runs.
+// ROWS (default mode): a token's 16 lanes exchange the query row first so that add instruction k covers columns 16 k + l16 of the lane group's
+// row — per wave-instruction 4 rows x one dense 64-byte segment = four 64-byte requests at the memory side, where component k of every lane's
+// float4 is 4 rows x 4 segments with 4 live dwords each = sixteen (tools/probes/atomic_shape_probe.hip: the time is per request).  The factors
+// are the same (dpos, dneg times one query value); every lane of the wave runs the exchange, a lane group without a target (gp == NULL) adds
+// nothing.  -DDR4SR_TABLE_ADDS_FLOAT4 builds the form before it for A / B runs; the deterministic instantiations keep it (they record, not add).
+#ifdef DR4SR_TABLE_ADDS_FLOAT4
+constexpr bool TABLE_ADD_ROWS = false;
+#else
+constexpr bool TABLE_ADD_ROWS = true;
+#endif
+// (experiments build, DR4SR_ROWADDS_SKIP: bit 1 -> TileAttnArgs::on bit 4, the launch is timed without TableAdds::issue; bit 2 ->
+// QkvEmbBwdArgs::xskip, without the embedding stage's dE adds — attribution only, the gradients are wrong.  Bit 0: attn_tile.h)
+#ifdef DR4SR_EXPERIMENTS
+#define XSKIP_TABLE(A_) (((A_).at.on & 16) != 0)
+#define XSKIP_EMB(A_) ((A_).xskip != 0)
+#else
+#define XSKIP_TABLE(A_) false
+#define XSKIP_EMB(A_) false
+#endif
 struct TableAdds {
     float* gp; float* gn; float dpos, dneg; float4 q;
+    template <bool ROWS>
     __device__ __forceinline__ void issue() const {
-        if (gp) {
+        if constexpr (ROWS) {
+            const int lane = threadIdx.x & 63, l16 = lane & 15, cc = l16 & 3;
+            float qc[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {                    // column 16 k + l16 = component l16 & 3 of lane 4 k + (l16 >> 2) of this lane group
+                const int src = (lane & 48) | (4 * k + (l16 >> 2));
+                const float x = __shfl(q.x, src, 64), y = __shfl(q.y, src, 64), z = __shfl(q.z, src, 64), w = __shfl(q.w, src, 64);
+                qc[k] = cc == 0 ? x : (cc == 1 ? y : (cc == 2 ? z : w));
+            }
+            if (gp) {
+                float* rp = gp - 3 * l16;                    // gp = row + 4 l16 (score_tile_regs' c): rp = row + l16
+                float* rn = gn - 3 * l16;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) unsafeAtomicAdd(rp + 16 * k, dpos * qc[k]);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) unsafeAtomicAdd(rn + 16 * k, dneg * qc[k]);
+            }
+        } else if (gp) {
             unsafeAtomicAdd(gp, dpos * q.x); unsafeAtomicAdd(gp + 1, dpos * q.y); unsafeAtomicAdd(gp + 2, dpos * q.z); unsafeAtomicAdd(gp + 3, dpos * q.w);
             unsafeAtomicAdd(gn, dneg * q.x); unsafeAtomicAdd(gn + 1, dneg * q.y); unsafeAtomicAdd(gn + 2, dneg * q.z); unsafeAtomicAdd(gn + 3, dneg * q.w);
         }
@@ -1042,7 +1079,7 @@ __device__ __forceinline__ void post_bwd_body(const PostArgs& A, const int t0, c
     // (the in-tile attention backward) reads LDS and only stores and adds, so nothing waits for these adds before the launch ends.  Right
     // behind out_proj's fragment request the last fragments of that GEMM and the ctx rows would still wait for them: the compiler counts
     // the adds of a divergent branch as not issued, and its vmcnt(0) in front of the last fragment covers them (measured equal or slower)
-    if constexpr (PF64) { if (ta) { __builtin_amdgcn_sched_barrier(0); ta->issue(); __builtin_amdgcn_sched_barrier(0); } }
+    if constexpr (PF64) { if (ta && !XSKIP_TABLE(A)) { __builtin_amdgcn_sched_barrier(0); ta->issue<!DET && TABLE_ADD_ROWS>(); __builtin_amdgcn_sched_barrier(0); } }
     if constexpr (AT) {
         if (at_on) {
             STAMP(17);
@@ -1476,7 +1513,7 @@ __device__ __forceinline__ void score_tile_regs(const PostArgs& A, const ScoreTi
                 float* gp = S.dE + tgt * D + c;
                 float* gn = S.dE + ng * D + c;
                 if (!S.rec && ta) {
-                    ta->gp = gp; ta->gn = gn; ta->dpos = dpos; ta->dneg = dneg; ta->q = q;
+                    ta->gp = gp; ta->gn = gn; ta->dpos = dpos; ta->dneg = dneg; ta->q = q;          // gp, gn: row + c with c = 4 (threadIdx.x & 15) — TableAdds::issue<true> relies on it
                 } else if (!S.rec) {
                     unsafeAtomicAdd(gp, dpos * q.x); unsafeAtomicAdd(gp + 1, dpos * q.y); unsafeAtomicAdd(gp + 2, dpos * q.z); unsafeAtomicAdd(gp + 3, dpos * q.w);
                     unsafeAtomicAdd(gn, dneg * q.x); unsafeAtomicAdd(gn + 1, dneg * q.y); unsafeAtomicAdd(gn + 2, dneg * q.z); unsafeAtomicAdd(gn + 3, dneg * q.w);
@@ -1588,6 +1625,7 @@ PostArgs make_post_args(const dr4sr_sasrec_plan* p, const Workspace& ws, int lay
     const bool near_ok = p->expected_tokens > 0 && p->expected_tokens <= 16 * (int64_t)p->B;
     if (A.at.on && !DR4SR_XENV("DR4SR_ATTN_TILE_FULL") && ((near_ok && p->D == 128) || DR4SR_XENV("DR4SR_ATTN_TILE_NEAR"))) A.at.on |= 4;
     if (A.at.on && DR4SR_ENV("DR4SR_ATTN_TILE_ATOMICS")) A.at.on |= 2;       // cross-check: every dK | dV row through atomics (no plain stores)
+    if (A.at.on && DR4SR_XENV("DR4SR_ROWADDS_SKIP")) A.at.on |= (atoi(DR4SR_XENV("DR4SR_ROWADDS_SKIP")) & 3) << 3;   // attribution: bit 3 no dK | dV adds, bit 4 no table adds
     A.at.qkv = lw.qkv; A.at.dqkv = lw.dqkv; A.at.ctx = lw.ctx; A.at.stat = lw.attn_st; A.at.tok = ws.tok; A.at.L = p->L; A.at.keep = lw.attn_keep;
     A.wt_attn = attn_fold_fwd(p, ws) ? 1 : 0;
     A.sp = wsplit_of(p, ws, layer);
@@ -1781,6 +1819,13 @@ int launch_qkv_bwd(const dr4sr_sasrec_plan* p, const Workspace& ws, int layer, h
 // WGT (A.inw, input_weight; instantiations of their own): where g = dx0 * mask exists, d_inw[b][pos] = <g, E[id] + P[pos]> (the forward's clamped id)
 // is STORED first — one value per valid token, by the first lane of the token's lane group, when A.d_inw is set —, then g <- inw[b][pos] * g, and only
 // then come the consumers of g below (gout plane, LDS-merged dE atomics, dP): the tables pick the factor up with no change to their jobs.
+// dE adds of the merged rows, default mode: single columns per lane (dense 64-byte segments per add instruction, as TableAdds::issue);
+// -DDR4SR_EMB_ADDS_FLOAT4 builds the form before it (the four components of a lane's float4 in four instructions) for A / B runs.
+#ifdef DR4SR_EMB_ADDS_FLOAT4
+constexpr bool EMB_ADD_ROWS = false;
+#else
+constexpr bool EMB_ADD_ROWS = true;
+#endif
 template <int BM, int D, bool DET = false, bool WGT = false>
 __device__ __forceinline__ void qkv_embed_bwd_body(const QkvEmbBwdArgs& A, const int t0, const int T) {
     constexpr int K = 3 * D, LDA = K + 4, LDC = D + 4, LPT = D / 4, TPB = 256 / LPT;
@@ -1858,13 +1903,32 @@ __device__ __forceinline__ void qkv_embed_bwd_body(const QkvEmbBwdArgs& A, const
             for (int q = 0; q < BM; ++q) same |= (unsigned long long)(ids[q] == id) << q;
         }
         if (id > 0 && (same & ((1ull << r) - 1ull)) == 0) {  // no earlier row with this id: this row carries the sum
+            if constexpr (!DET && BM == 16 && EMB_ADD_ROWS) {      // (the latency forms)
+                // the lane group reads single columns of the rows in LDS: add instruction k covers columns LPT k + j of its row — dense 64-byte
+                // segments (TableAdds above) —, every element the same sum in the same order as the float4 form below
+                const int j = threadIdx.x % LPT;
+                float gk[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) gk[k] = Cs[r * LDC + LPT * k + j];
+                for (same = r + 1 < 64 ? same >> (r + 1) : 0; same; same &= same - 1) {
+                    const int q = r + __ffsll((long long)same);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) gk[k] += Cs[q * LDC + LPT * k + j];
+                }
+                float* d = A.dE + (size_t)id * D + j;
+                if (!XSKIP_EMB(A)) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) unsafeAtomicAdd(d + LPT * k, gk[k]);
+                }
+                continue;
+            }
             float4 g = ld4(Cs + r * LDC + c);
             for (same = r + 1 < 64 ? same >> (r + 1) : 0; same; same &= same - 1) {
                 const int q = r + __ffsll((long long)same);
                 const float4 o = ld4(Cs + q * LDC + c); g.x += o.x; g.y += o.y; g.z += o.z; g.w += o.w;
             }
             float* d = A.dE + (size_t)id * D + c;
-            unsafeAtomicAdd(d, g.x); unsafeAtomicAdd(d + 1, g.y); unsafeAtomicAdd(d + 2, g.z); unsafeAtomicAdd(d + 3, g.w);
+            if (!XSKIP_EMB(A)) { unsafeAtomicAdd(d, g.x); unsafeAtomicAdd(d + 1, g.y); unsafeAtomicAdd(d + 2, g.z); unsafeAtomicAdd(d + 3, g.w); }
         }
     }
     for (int i = threadIdx.x; i < A.L * D; i += 256) {
@@ -1889,6 +1953,9 @@ static QkvEmbBwdArgs make_qeb_args(const dr4sr_sasrec_plan* p, const Workspace& 
     A.kv_part = (ws.det_lat && ws.det_kv && attn_in_tile(p, ws)) ? ws.det_kv : nullptr; A.tok = ws.tok;
     A.sp = wsplit_of(p, ws, 0);
     A.inw = inw; A.d_inw = inw ? d_inw : nullptr; A.E = p->params + ws.off[0]; A.P = p->params + ws.off[1];
+#ifdef DR4SR_EXPERIMENTS
+    A.xskip = DR4SR_XENV("DR4SR_ROWADDS_SKIP") ? (atoi(DR4SR_XENV("DR4SR_ROWADDS_SKIP")) & 4) : 0;
+#endif
     return A;
 }
 // latency regime: k_qkv_embed_bwd and k_wgrad are independent (the weight gradients read dqkv / X, not dx0), so the embedding tiles
