@@ -187,7 +187,8 @@ __global__ __launch_bounds__(1024) void k_fmlp_prep(const FPrepArgs A) {
 // dm[layer][i] = sum over the nblk per-workgroup partials written by k_fmlp_filter_bwd (fixed order -> deterministic).
 // History of this launch: one thread walking all 256 partials of a column (26 workgroups): 60 us of dependent-latency loads; 64
 // columns per workgroup, partials split over 4 waves, 8 four-byte loads in flight per thread: 19.5 us; now 6.1 us (below).
-// blockIdx.y == n_layer: the slab of the position-table gradient partials left by k_fmlp_embed_bwd -> dP (this launch is its only writer)
+// blockIdx.y == n_layer: the slab of the position-table gradient partials left by k_fmlp_embed_bwd, ADDED into dP (gradients accumulate across
+// calls; within a call this launch is dP's only writer, so the sum stays a fixed-order one)
 // Thread = (4 columns, one of 16 partial sub-rows): 16-byte loads, 4 in flight per thread (16 KB per workgroup: the launch is bound
 // by the bytes it keeps in flight, 9.8 MB through ~2 us round trips), then the 16 sub-rows meet in LDS in a fixed order.
 // blockIdx.x >= nx (two more blocks per slab): the LayerNorm weight | bias partials of the same workgroups (ln_wg) -> grads; 256
@@ -223,10 +224,11 @@ __global__ __launch_bounds__(256) void k_fmlp_dm_reduce(const FDmRedArgs A) {
         float4 s4 = red[0][c4];
 #pragma unroll
         for (int k = 1; k < 16; ++k) { const float4 v = red[k][c4]; s4.x += v.x; s4.y += v.y; s4.z += v.z; s4.w += v.w; }
-        if (!ln) st4((layer == A.n_layer ? A.dP : A.dm + (size_t)layer * n) + i, s4);
-        else {                                             // this launch is the only writer of these rows of the step's gradient
+        if (!ln && layer != A.n_layer) st4(A.dm + (size_t)layer * n + i, s4);       // dm is workspace: stored
+        else {                                             // gradient rows ACCUMULATE (include/dr4sr_hip.h); this launch is their only writer within a call
             const bool wgt = i < FM_D;
-            float* g = A.grads + (layer == A.n_layer ? (wgt ? A.o_eln_w : A.o_eln_b) : (wgt ? A.o_fln_w : A.o_fln_b) + layer * A.layer_stride) + (wgt ? i : i - FM_D);
+            float* g = !ln ? A.dP + i
+                           : A.grads + (layer == A.n_layer ? (wgt ? A.o_eln_w : A.o_eln_b) : (wgt ? A.o_fln_w : A.o_fln_b) + layer * A.layer_stride) + (wgt ? i : i - FM_D);
             const float4 o = ld4(g);
             st4(g, make_float4(o.x + s4.x, o.y + s4.y, o.z + s4.z, o.w + s4.w));
         }
