@@ -126,6 +126,20 @@ class LayerGrads(C.Structure):
     _fields_ = [(n, _f32p) for n in LAYER_TENSORS]
 
 
+FMLP_LAYER_TENSORS = ("complex_weight", "filter_ln_weight", "filter_ln_bias", "dense_1_weight", "dense_1_bias", "dense_2_weight", "dense_2_bias",
+                      "inter_ln_weight", "inter_ln_bias")
+
+
+class FmlpLayerWeights(C.Structure):
+    """mirror of `dr4sr_fmlp_layer_weights` (include/dr4sr_hip.h): the 9 tensors of one FMLP layer in the flat layout's order"""
+    _fields_ = [(n, _f32p) for n in FMLP_LAYER_TENSORS]
+
+
+class FmlpLayerGrads(C.Structure):
+    """mirror of `dr4sr_fmlp_layer_grads` (include/dr4sr_hip.h): the same 9, writable"""
+    _fields_ = [(n, _f32p) for n in FMLP_LAYER_TENSORS]
+
+
 class MetaWeighting(C.Structure):
     """mirror of `dr4sr_meta_weighting` (include/dr4sr_hip.h)"""
     _fields_ = [("phi", _f32p), ("gumbel", _f32p), ("user_id", _i64p), ("gate_in", C.c_void_p), ("gate_out", C.c_void_p),
@@ -356,6 +370,18 @@ SYMBOLS = {
     "dr4sr_seq_pool_bwd": (C.c_int, [_f32p, _i64p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _f32p, C.c_void_p]),
     "dr4sr_dropout_apply": (C.c_int, [_f32p, C.c_int64, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, _f32p, C.c_void_p]),
     "dr4sr_embed_gather_posadd_bwd": (C.c_int, [_f32p, _i64p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p, _f32p, C.c_void_p]),
+    # additive to ABI 10: the stateless FMLP layer op and the LayerNorm op on dense tensors (csrc/fmlp_op.hip)
+    "dr4sr_fmlp_layer_saved_floats": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "dr4sr_fmlp_layer_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "dr4sr_fmlp_layer_fwd": (C.c_int, [_f32p, C.POINTER(FmlpLayerWeights), C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                       C.c_uint64, C.c_uint32, C.c_int32, _f32p, _f32p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "dr4sr_fmlp_layer_bwd": (C.c_int, [_f32p, C.POINTER(FmlpLayerWeights), C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                       C.c_uint64, C.c_uint32, C.c_int32, _f32p, _f32p, _f32p, C.POINTER(FmlpLayerGrads), C.c_void_p, C.c_int64,
+                                       C.c_void_p]),
+    "dr4sr_layer_norm_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
+    "dr4sr_layer_norm_fwd": (C.c_int, [_f32p, _f32p, _f32p, C.c_int64, C.c_int32, C.c_float, _f32p, C.c_void_p]),
+    "dr4sr_layer_norm_bwd": (C.c_int, [_f32p, _f32p, C.c_int64, C.c_int32, C.c_float, _f32p, _f32p, _f32p, _f32p, C.c_void_p, C.c_int64,
+                                       C.c_void_p]),
 }
 
 _lib = None
@@ -369,7 +395,9 @@ class Dr4srError(RuntimeError):
 # tree's own library must export them like every other symbol
 _AFTER_PARENT_AB = ("dr4sr_sasrec_encode_w", "dr4sr_sasrec_encode_w_bwd", "dr4sr_mine_workspace_bytes", "dr4sr_mine_patterns",
                     "dr4sr_sasrec_layer_saved_floats", "dr4sr_sasrec_layer_workspace_bytes", "dr4sr_sasrec_layer_fwd", "dr4sr_sasrec_layer_bwd",
-                    "dr4sr_seq_pool_fwd", "dr4sr_seq_pool_bwd", "dr4sr_dropout_apply", "dr4sr_embed_gather_posadd_bwd")
+                    "dr4sr_seq_pool_fwd", "dr4sr_seq_pool_bwd", "dr4sr_dropout_apply", "dr4sr_embed_gather_posadd_bwd",
+                    "dr4sr_fmlp_layer_saved_floats", "dr4sr_fmlp_layer_workspace_bytes", "dr4sr_fmlp_layer_fwd", "dr4sr_fmlp_layer_bwd",
+                    "dr4sr_layer_norm_workspace_bytes", "dr4sr_layer_norm_fwd", "dr4sr_layer_norm_bwd")
 
 
 def load():

@@ -11,7 +11,13 @@ Dropout runs through the library's Philox masks, keyed by (seed, step, site): th
 torch.ops.dr4sr_hip.dropout at DR4SR_SITE_EMB, the layers draw their four sites themselves.  `step` is an explicit counter: every
 training forward uses self.step and then advances it by one, so two forwards never share masks and a run is reproducible from (seed,
 step).  A query position with no admissible key (a padded row on the id path) gets a zero attention context where torch yields NaN; the
-reference never reads such a position."""
+reference never reads such a position.
+
+FMLPEncoderOps / FMLPOps — the reference's FMLPEncoder (module/layers.py:740-808) and the encoder half of its FMLP model (model/fmlp.py:8-39)
+written the same way: each `Layer` (FilterLayer + Intermediate) is one torch.ops.dr4sr_hip.fmlp_layer (csrc/fmlp_op.hip), the embedding
+LayerNorm torch.ops.dr4sr_hip.layer_norm.  Parameters carry the reference's names, so a checkpoint of the engine-backed FMLP loads with
+strict=True (its `item_embedding.weight` is the table the module is handed).  The dropout sites are the FMLP engine's: 0 for the
+embedding, 1 + 2 l and 2 + 2 l for layer l; the step counter works as above."""
 from __future__ import annotations
 
 import torch
@@ -108,3 +114,87 @@ class SASRecQueryEncoderOps(nn.Module):
             return x
         kind = self.training_pooling_type if self.training else self.eval_pooling_type
         return o.seq_pool(x, batch["seqlen"], _POOLING[kind])
+
+
+class _FilterLayer(nn.Module):
+    """FilterLayer's parameters (module/layers.py:740-745): complex_weight [1, L/2 + 1, D, 2] = randn * 0.02, LayerNorm"""
+    def __init__(self, L, D):
+        super().__init__()
+        self.complex_weight = nn.Parameter(torch.randn(1, L // 2 + 1, D, 2, dtype=torch.float32) * 0.02)
+        self.LayerNorm = nn.LayerNorm(D, eps=1e-12)
+
+
+class _Intermediate(nn.Module):
+    """Intermediate's parameters (module/layers.py:761-769)"""
+    def __init__(self, D):
+        super().__init__()
+        self.dense_1 = nn.Linear(D, 4 * D)
+        self.dense_2 = nn.Linear(4 * D, D)
+        self.LayerNorm = nn.LayerNorm(D, eps=1e-12)
+
+
+class _FMLPLayer(nn.Module):
+    def __init__(self, L, D):
+        super().__init__()
+        self.filterlayer = _FilterLayer(L, D)
+        self.intermediate = _Intermediate(D)
+
+    def tensors(self):
+        """the 9 tensors in the flat layout's order (include/dr4sr_hip.h dr4sr_fmlp_layer_weights)"""
+        f, i = self.filterlayer, self.intermediate
+        return (f.complex_weight, f.LayerNorm.weight, f.LayerNorm.bias, i.dense_1.weight, i.dense_1.bias, i.dense_2.weight, i.dense_2.bias,
+                i.LayerNorm.weight, i.LayerNorm.bias)
+
+
+class FMLPEncoderOps(nn.Module):
+    """FMLPEncoder (module/layers.py:793-808): `num_hidden_layers` copies of ONE initialised Layer, as copy.deepcopy gives the reference.
+    The reference hard-codes 50 positions, 64 features, dropout 0.5 and eps 1e-12; they are keyword arguments here.  p_drop applies in
+    train mode only; seed / step key the masks and are set by the owner (FMLPOps) or the caller"""
+    def __init__(self, num_hidden_layers=2, max_seq_len=50, hidden_size=64, dropout=0.5, layer_norm_eps=1e-12, seed: int = 2023) -> None:
+        super().__init__()
+        first = _FMLPLayer(max_seq_len, hidden_size)
+        self.layer = nn.ModuleList([first] + [_FMLPLayer(max_seq_len, hidden_size) for _ in range(num_hidden_layers - 1)])
+        for other in self.layer[1:]:
+            other.load_state_dict(first.state_dict())
+        self.p_drop, self.eps = float(dropout), float(layer_norm_eps)
+        self.seed, self.step = int(seed), 0
+
+    def forward(self, hidden_states, output_all_encoded_layers=True):
+        p = self.p_drop if self.training else 0.0
+        all_encoder_layers = []
+        for i, layer in enumerate(self.layer):
+            hidden_states, _ = torch.ops.dr4sr_hip.fmlp_layer(hidden_states, *layer.tensors(), self.eps, p, self.seed, self.step, i)
+            if output_all_encoded_layers:
+                all_encoder_layers.append(hidden_states)
+        if not output_all_encoded_layers:
+            all_encoder_layers.append(hidden_states)
+        return all_encoder_layers
+
+
+class FMLPOps(nn.Module):
+    """the encoder of the reference's FMLP (model/fmlp.py:8-39) on `item_embedding` (an nn.Embedding the caller owns): position_embeddings,
+    LayerNorm and item_encoder under the reference's names; forward(batch) is fmlp.py:30-39, the query x[:, -1] (need_pooling=False returns
+    the last layer's [B, L, D])"""
+    def __init__(self, item_embedding, n_layer, max_seq_len=50, dropout=0.5, layer_norm_eps=1e-12, seed: int = 2023, fiid="item_id") -> None:
+        super().__init__()
+        D = item_embedding.weight.shape[1]
+        self.fiid = fiid
+        self.item_embedding = item_embedding
+        self.position_embeddings = nn.Embedding(max_seq_len, D)
+        self.LayerNorm = nn.LayerNorm(D, eps=layer_norm_eps)
+        self.item_encoder = FMLPEncoderOps(n_layer, max_seq_len, D, dropout, layer_norm_eps, seed)
+        self.p_drop, self.eps = float(dropout), float(layer_norm_eps)
+        self.seed, self.step = int(seed), 0
+
+    def forward(self, batch, need_pooling=True):
+        o = torch.ops.dr4sr_hip
+        p = self.p_drop if self.training else 0.0
+        x = o.embed_gather_posadd(self.item_embedding.weight, self.position_embeddings.weight, batch["in_" + self.fiid])     # fmlp.py:18-24
+        x = o.layer_norm(x, self.LayerNorm.weight, self.LayerNorm.bias, self.eps)                                            # fmlp.py:25
+        if p > 0.0:                                                                                                          # fmlp.py:26
+            x = o.dropout(x, p, self.seed, self.step, _lib.SITE_EMB)
+        self.item_encoder.seed, self.item_encoder.step = self.seed, self.step
+        x = self.item_encoder(x, output_all_encoded_layers=True)[-1]
+        if self.training:
+            self.step += 1
+        return x[:, -1] if need_pooling else x

@@ -19,11 +19,17 @@ a reference-style model written against plain torch ops:
                                                               (autograd: d x and the 12 weight gradients, bit-reproducible)
     seq_pool(x, seqlen, pooling) -> out                       module/layers.py:41-73 'origin' | 'last', module/functional.py:50-55 'mean'
     dropout(x, p_drop, seed, step, site) -> out               model/sasrec.py:66 with the library's Philox masks (DR4SR_SITE_EMB)
-    (+ embed_gather_posadd_backward, sasrec_layer_backward, seq_pool_backward: the autograd formulas, ops themselves)
+    fmlp_layer(x, complex_weight, filter_ln_w, filter_ln_b, dense_1_w, dense_1_b, dense_2_w, dense_2_b, inter_ln_w, inter_ln_b,
+               eps, p_drop, seed, step, layer) -> (y, saved)  one FMLP Layer (FilterLayer + Intermediate) of module/layers.py:740-791 on dense
+                                                              [B, L, 64] (autograd: d x and the 9 weight gradients, bit-reproducible)
+    layer_norm(x, weight, bias, eps) -> y                     nn.LayerNorm over the last dimension: model/fmlp.py:25 (autograd: d x, d w, d b)
+    (+ embed_gather_posadd_backward, sasrec_layer_backward, seq_pool_backward, fmlp_layer_backward, layer_norm_backward: the autograd
+     formulas, ops themselves)
 
 Every implementation only enqueues HIP kernels of libdr4sr_hip.so on the current stream; there is no CPU kernel (the ops raise on
 CPU tensors).  The encoder LAYER is a dispatcher op: stateless, dense tensors in and out, its dropout keyed by explicit (seed, step,
-layer) arguments — dr4sr_amd/module/layers.py SASRecQueryEncoderOps is the reference's query encoder written on these ops.  What stays
+layer) arguments — dr4sr_amd/module/layers.py SASRecQueryEncoderOps is the reference's query encoder written on these ops, FMLPOps /
+FMLPEncoderOps the reference's FMLP on fmlp_layer and layer_norm.  What stays
 outside the dispatcher are the plan-based entry points (whole fused training steps, the packed encoders with their workspaces), driven by
 the engines (dr4sr_amd/engine.py ...): they own device state (workspace, RNG step, Adam step).
 """
@@ -480,6 +486,163 @@ def _drop_backward(ctx, g):
 dropout.register_autograd(_drop_backward, setup_context=_drop_setup)
 
 
+# ------------------------------------------------------------------------------------------------ FMLP layer / LayerNorm
+def _fmlp_dims(x, complex_weight, dense_1_weight):
+    if x.dim() != 3 or x.dtype != torch.float32:
+        raise _lib.Dr4srError("fmlp_layer: x must be a [B, L, D] float32 tensor")
+    B, L, D = (int(s) for s in x.shape)
+    F = int(dense_1_weight.shape[0])
+    n = int(_lib.load().dr4sr_fmlp_layer_saved_floats(B, L, D, F))          # the shape refusals (DR4SR_E_SHAPE), before any launch
+    _lib.check(min(n, 0), "dr4sr_fmlp_layer_saved_floats")
+    if tuple(complex_weight.shape) != (1, L // 2 + 1, D, 2):
+        raise _lib.Dr4srError(f"fmlp_layer: complex_weight must be [1, L/2 + 1, D, 2] = {(1, L // 2 + 1, D, 2)}, got {tuple(complex_weight.shape)}")
+    return B, L, D, F, n
+
+
+def _fmlp_ws(lib, B, L, D, F, backward, device):
+    nb = int(lib.dr4sr_fmlp_layer_workspace_bytes(B, L, D, F, backward))
+    _lib.check(min(nb, 0), "dr4sr_fmlp_layer_workspace_bytes")
+    return torch.empty(max(nb // 4, 1), dtype=torch.float32, device=device), nb
+
+
+@torch.library.custom_op(f"{NS}::fmlp_layer", mutates_args=())
+def fmlp_layer(x: torch.Tensor, complex_weight: torch.Tensor, filter_ln_weight: torch.Tensor, filter_ln_bias: torch.Tensor,
+               dense_1_weight: torch.Tensor, dense_1_bias: torch.Tensor, dense_2_weight: torch.Tensor, dense_2_bias: torch.Tensor,
+               inter_ln_weight: torch.Tensor, inter_ln_bias: torch.Tensor, eps: float, p_drop: float, seed: int, step: int,
+               layer: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """one FMLP Layer (module/layers.py:781-791) on x [B, L, 64], L even and <= 64; complex_weight [1, L/2 + 1, 64, 2] as the reference
+    holds it.  Dropout sites 1 + 2 layer (filter) and 2 + 2 layer (FFN) of stream (seed, step).  `saved` is the opaque buffer the backward
+    reads"""
+    ws_ = (complex_weight, filter_ln_weight, filter_ln_bias, dense_1_weight, dense_1_bias, dense_2_weight, dense_2_bias, inter_ln_weight,
+           inter_ln_bias)
+    _need_cuda(x, *ws_)
+    lib = _lib.load()
+    B, L, D, F, n = _fmlp_dims(x, complex_weight, dense_1_weight)
+    xc = x.contiguous()
+    wc = [t.contiguous() for t in ws_]
+    y = torch.empty_like(xc)
+    saved = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
+    ws, nb = _fmlp_ws(lib, B, L, D, F, 0, x.device)
+    w = _layer_struct(_lib.FmlpLayerWeights, wc)
+    _lib.check(lib.dr4sr_fmlp_layer_fwd(_lib.ptr(xc), w, B, L, D, F, eps, p_drop, seed & 0xFFFFFFFFFFFFFFFF, step & 0xFFFFFFFF, layer,
+                                        _lib.ptr(y), _lib.ptr(saved), _lib.ptr(ws), nb, _lib.cur_stream()), "dr4sr_fmlp_layer_fwd")
+    return y, saved
+
+
+@fmlp_layer.register_fake
+def _(x, complex_weight, filter_ln_weight, filter_ln_bias, dense_1_weight, dense_1_bias, dense_2_weight, dense_2_bias, inter_ln_weight,
+      inter_ln_bias, eps, p_drop, seed, step, layer):
+    B, L, D = x.shape
+    return torch.empty_like(x), x.new_empty(max(B * L * (2 * D + dense_1_weight.shape[0]), 1))
+
+
+@torch.library.custom_op(f"{NS}::fmlp_layer_backward", mutates_args=())
+def fmlp_layer_backward(x: torch.Tensor, complex_weight: torch.Tensor, filter_ln_weight: torch.Tensor, filter_ln_bias: torch.Tensor,
+                        dense_1_weight: torch.Tensor, dense_1_bias: torch.Tensor, dense_2_weight: torch.Tensor, dense_2_bias: torch.Tensor,
+                        inter_ln_weight: torch.Tensor, inter_ln_bias: torch.Tensor, eps: float, p_drop: float, seed: int, step: int,
+                        layer: int, saved: torch.Tensor, dy: torch.Tensor) -> List[torch.Tensor]:
+    """-> [dx, the 9 weight gradients in the argument order]; written, not accumulated; bit-reproducible"""
+    ws_ = (complex_weight, filter_ln_weight, filter_ln_bias, dense_1_weight, dense_1_bias, dense_2_weight, dense_2_bias, inter_ln_weight,
+           inter_ln_bias)
+    _need_cuda(x, saved, dy, *ws_)
+    lib = _lib.load()
+    B, L, D, F, _ = _fmlp_dims(x, complex_weight, dense_1_weight)
+    xc, dyc, sc = x.contiguous(), dy.contiguous().float(), saved.contiguous()
+    wc = [t.contiguous() for t in ws_]
+    dx = torch.empty_like(xc)
+    dws = [torch.empty_like(t) for t in wc]
+    ws, nb = _fmlp_ws(lib, B, L, D, F, 1, x.device)
+    w, g = _layer_struct(_lib.FmlpLayerWeights, wc), _layer_struct(_lib.FmlpLayerGrads, dws)
+    _lib.check(lib.dr4sr_fmlp_layer_bwd(_lib.ptr(xc), w, B, L, D, F, eps, p_drop, seed & 0xFFFFFFFFFFFFFFFF, step & 0xFFFFFFFF, layer,
+                                        _lib.ptr(sc), _lib.ptr(dyc), _lib.ptr(dx), g, _lib.ptr(ws), nb, _lib.cur_stream()),
+               "dr4sr_fmlp_layer_bwd")
+    return [dx] + dws
+
+
+@fmlp_layer_backward.register_fake
+def _(x, complex_weight, filter_ln_weight, filter_ln_bias, dense_1_weight, dense_1_bias, dense_2_weight, dense_2_bias, inter_ln_weight,
+      inter_ln_bias, eps, p_drop, seed, step, layer, saved, dy):
+    return [torch.empty_like(t) for t in (x, complex_weight, filter_ln_weight, filter_ln_bias, dense_1_weight, dense_1_bias, dense_2_weight,
+                                          dense_2_bias, inter_ln_weight, inter_ln_bias)]
+
+
+def _fmlp_setup(ctx, inputs, output):
+    ctx.rest = inputs[10:]                                  # eps, p_drop, seed, step, layer
+    ctx.save_for_backward(*inputs[:10], output[1])
+    ctx.mark_non_differentiable(output[1])
+
+
+def _fmlp_backward(ctx, g_y, g_saved):
+    x, *w, saved = ctx.saved_tensors
+    out = fmlp_layer_backward(x, *w, *ctx.rest, saved, g_y)
+    return (*out, None, None, None, None, None)
+
+
+fmlp_layer.register_autograd(_fmlp_backward, setup_context=_fmlp_setup)
+
+
+def _ln_dims(x, weight):
+    if x.dim() < 1 or x.dtype != torch.float32 or x.shape[-1] != weight.shape[0]:
+        raise _lib.Dr4srError("layer_norm: x must be a float32 tensor whose last dimension is the weight's")
+    D = int(x.shape[-1])
+    return x.numel() // max(D, 1), D
+
+
+@torch.library.custom_op(f"{NS}::layer_norm", mutates_args=())
+def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float) -> torch.Tensor:
+    """torch.nn.LayerNorm over the last dimension (a multiple of 4 up to 1024): FMLP's embedding LayerNorm, model/fmlp.py:25"""
+    _need_cuda(x, weight, bias)
+    lib = _lib.load()
+    n, D = _ln_dims(x, weight)
+    xc = x.contiguous()
+    y = torch.empty_like(xc)
+    _lib.check(lib.dr4sr_layer_norm_fwd(_lib.ptr(xc), _lib.ptr(weight.contiguous()), _lib.ptr(bias.contiguous()), n, D, eps, _lib.ptr(y),
+                                        _lib.cur_stream()), "dr4sr_layer_norm_fwd")
+    return y
+
+
+@layer_norm.register_fake
+def _(x, weight, bias, eps):
+    return torch.empty_like(x)
+
+
+@torch.library.custom_op(f"{NS}::layer_norm_backward", mutates_args=())
+def layer_norm_backward(x: torch.Tensor, weight: torch.Tensor, eps: float, dy: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (dx, d weight, d bias); written, not accumulated; bit-reproducible"""
+    _need_cuda(x, weight, dy)
+    lib = _lib.load()
+    n, D = _ln_dims(x, weight)
+    nb = int(lib.dr4sr_layer_norm_workspace_bytes(n, D))
+    _lib.check(min(nb, 0), "dr4sr_layer_norm_workspace_bytes")
+    xc, wc, dyc = x.contiguous(), weight.contiguous(), dy.contiguous().float()
+    dx, dw, db = torch.empty_like(xc), torch.empty_like(wc), torch.empty_like(wc)
+    ws = torch.empty(max(nb // 4, 1), dtype=torch.float32, device=x.device)
+    _lib.check(lib.dr4sr_layer_norm_bwd(_lib.ptr(xc), _lib.ptr(wc), n, D, eps, _lib.ptr(dyc), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db),
+                                        _lib.ptr(ws), nb, _lib.cur_stream()), "dr4sr_layer_norm_bwd")
+    return dx, dw, db
+
+
+@layer_norm_backward.register_fake
+def _(x, weight, eps, dy):
+    return torch.empty_like(x), torch.empty_like(weight), torch.empty_like(weight)
+
+
+def _ln_setup(ctx, inputs, output):
+    x, weight, _, eps = inputs
+    ctx.eps = eps
+    ctx.save_for_backward(x, weight)
+
+
+def _ln_backward(ctx, g):
+    x, weight = ctx.saved_tensors
+    dx, dw, db = layer_norm_backward(x, weight, ctx.eps, g)
+    return dx, dw, db, None
+
+
+layer_norm.register_autograd(_ln_backward, setup_context=_ln_setup)
+
+
 OPS = ("embed_gather_posadd", "score_bce", "score_bce_backward", "score_bpr", "score_bpr_backward", "loss_from_scores",
        "loss_from_scores_backward", "neg_sample", "full_score_topk", "target_rank", "fused_adam_",
-       "sasrec_layer", "sasrec_layer_backward", "seq_pool", "seq_pool_backward", "dropout", "embed_gather_posadd_backward")
+       "sasrec_layer", "sasrec_layer_backward", "seq_pool", "seq_pool_backward", "dropout", "embed_gather_posadd_backward",
+       "fmlp_layer", "fmlp_layer_backward", "layer_norm", "layer_norm_backward")

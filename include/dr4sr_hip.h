@@ -957,6 +957,58 @@ int dr4sr_dropout_apply(const float* x, int64_t n, float p_drop, uint64_t seed, 
 int dr4sr_embed_gather_posadd_bwd(const float* dx, const int64_t* idx, int64_t B, int32_t L, int32_t D, int32_t n_items, int32_t n_pos,
                                   float* dE, float* dP, void* stream);
 
+/* ---- additive to ABI 10: the stateless FMLP layer op and the LayerNorm op on dense tensors (csrc/fmlp_op.hip; what
+ * torch.ops.dr4sr_hip.fmlp_layer / layer_norm run).  No plan, no workspace that survives a call, no device state words.
+ *
+ * The layer is ONE FMLP `Layer` of the reference (module/layers.py:781-791) on x [B, L, D] fp32, contiguous:
+ *     f  = irfft(rfft(x, dim=1, 'ortho') * view_as_complex(complex_weight), n=L, dim=1, 'ortho')
+ *     xf = LayerNorm_f(drop_FILT(f) + x)
+ *     y  = LayerNorm_i(drop_FFN(dense_2(gelu_erf(dense_1(xf)))) + xf)          (no dropout behind the GELU, as in the reference)
+ * complex_weight is [1, L/2 + 1, D, 2] (re | im innermost), the LayerNorm tensors [D], dense_1 [F, D] | [F], dense_2 [D, F] | [D]; LayerNorm
+ * eps from the caller.  The filter is computed as the per-feature circular convolution it equals (csrc/fmlp.hip): the imaginary parts
+ * of the DC and Nyquist bins contribute nothing and receive a zero gradient, as in torch.
+ * Supported shapes (anything else: DR4SR_E_SHAPE, before any launch): D = 64, F = 256, L even, 2 <= L <= 64.  DR4SR_E_ARG: a null
+ * pointer (in the forward, saved may be NULL), B < 0, p_drop outside [0, 1), eps < 0, layer outside [0, 1024].  A null or too small
+ * workspace (dr4sr_fmlp_layer_workspace_bytes with backward = 0 for the forward, 1 for the backward): DR4SR_E_WS; nothing in it survives a
+ * call.  B = 0 launches nothing (the backward zero-fills dw); the activation pointers and the workspace may then be null.
+ *
+ * Dropout: the two sites 1 + 2 * layer (behind the filter) and 2 + 2 * layer (behind dense_2) of the library's Philox stream keyed by
+ * (seed, step, site) — the numbering of the FMLP engine, site 0 being its embedding dropout; the decision of an element is that of
+ * element e = (b * L + pos) * D + c of the hooks header's dr4sr_dropout_mask for the same (p, seed, step, site), which is what the engine
+ * draws on a plan without `rows`.  p_drop == 0 does no RNG work.
+ *
+ * saved (forward: written when non-NULL; backward: read) is opaque, dr4sr_fmlp_layer_saved_floats floats (both LayerNorm inputs and the
+ * FFN pre-activation): NULL for inference.  The backward takes the inputs of the forward it differentiates; dx and the 9 tensors of dw
+ * are WRITTEN, not accumulated.  It uses no float atomics: every workgroup sums the sequences it owns in index order into its slot of
+ * ws, a second launch adds the slots in index order and folds the filter-kernel gradient back to d complex_weight — two calls give the
+ * same bits.  Launches on `stream` only (capturable), no allocation, no host synchronisation. */
+typedef struct dr4sr_fmlp_layer_weights {  /* the layer tensors in the flat layout's order (dr4sr_fmlp_param_layout) */
+    const float *complex_weight, *filter_ln_weight, *filter_ln_bias, *dense_1_weight, *dense_1_bias, *dense_2_weight, *dense_2_bias,
+        *inter_ln_weight, *inter_ln_bias;
+} dr4sr_fmlp_layer_weights;
+typedef struct dr4sr_fmlp_layer_grads {
+    float *complex_weight, *filter_ln_weight, *filter_ln_bias, *dense_1_weight, *dense_1_bias, *dense_2_weight, *dense_2_bias,
+        *inter_ln_weight, *inter_ln_bias;
+} dr4sr_fmlp_layer_grads;
+/* floats / bytes, or a negative DR4SR_E_* code */
+int64_t dr4sr_fmlp_layer_saved_floats(int64_t B, int32_t L, int32_t D, int32_t F);
+int64_t dr4sr_fmlp_layer_workspace_bytes(int64_t B, int32_t L, int32_t D, int32_t F, int32_t backward);
+int dr4sr_fmlp_layer_fwd(const float* x, const dr4sr_fmlp_layer_weights* w, int64_t B, int32_t L, int32_t D, int32_t F, float eps,
+                         float p_drop, uint64_t seed, uint32_t step, int32_t layer, float* y, float* saved, void* ws, int64_t ws_bytes,
+                         void* stream);
+int dr4sr_fmlp_layer_bwd(const float* x, const dr4sr_fmlp_layer_weights* w, int64_t B, int32_t L, int32_t D, int32_t F, float eps,
+                         float p_drop, uint64_t seed, uint32_t step, int32_t layer, const float* saved, const float* dy, float* dx,
+                         const dr4sr_fmlp_layer_grads* dw, void* ws, int64_t ws_bytes, void* stream);
+/* torch.nn.LayerNorm over the last dimension of x [n_rows, D] (FMLP's embedding LayerNorm, model/fmlp.py:25): biased variance, eps from
+ * the caller, D a multiple of 4 up to 1024 (else DR4SR_E_SHAPE).  The backward recomputes the statistics from x and WRITES dx, dw and db
+ * (slots of ws summed in index order: two calls give the same bits).  A null pointer, n_rows < 0, eps < 0: DR4SR_E_ARG; a null or too
+ * small ws (dr4sr_layer_norm_workspace_bytes): DR4SR_E_WS.  n_rows = 0 launches nothing (the backward zero-fills dw and db). */
+int64_t dr4sr_layer_norm_workspace_bytes(int64_t n_rows, int32_t D);
+int dr4sr_layer_norm_fwd(const float* x, const float* weight, const float* bias, int64_t n_rows, int32_t D, float eps, float* y,
+                         void* stream);
+int dr4sr_layer_norm_bwd(const float* x, const float* weight, int64_t n_rows, int32_t D, float eps, const float* dy, float* dx, float* dw,
+                         float* db, void* ws, int64_t ws_bytes, void* stream);
+
 /* Test / measurement hooks (dr4sr_dropout_mask, dr4sr_*_launch_kernel) are NOT part of this product surface: they are declared in
  * include/dr4sr_hip_hooks.h, and nothing under dr4sr_amd/ calls them. */
 
