@@ -18,6 +18,9 @@
 // Weight gradients: every workgroup sums the sequences it owns, in that order, into its own slot of the workspace (dm [L][64] and the
 // other eight tensors); a second launch adds the slots in index order and folds dm back to d complex_weight — no float atomics, the same
 // bits on every call.
+//
+// This file holds the filter half of the layer (its first rows pass runs in the convolution's thread layout) and the LayerNorm op; the
+// FFN + LayerNorm_i half, forward and backward, and the slot reduction are op_tiles.h's (shared with layer_op.hip).
 #include "common.h"
 #include "fmlp_conv.h"
 #include "op_tiles.h"
@@ -26,7 +29,6 @@ namespace fop {
 using namespace optile;
 
 constexpr int D = 64, F = 256, LDX = D + 4, LDF = F + 4;
-constexpr int MAX_SLOTS = 256;         // workgroups (= weight-gradient partial slots) of a backward launch
 constexpr int M_FLOATS = 64 * D;       // the filter kernel m, L <= 64 rows
 constexpr int R_FLOATS = 64 * LDF;     // >= 2 * (2 * 64) * D: X2 and DY2 of the filter phases
 constexpr int LDS_FLOATS = 2 * 64 * LDX + R_FLOATS + M_FLOATS + 2 * 128;
@@ -66,9 +68,10 @@ __global__ __launch_bounds__(256) void k_fmlp_op_coef(const float* __restrict__ 
     m[i] = acc / (float)L;
 }
 
-__device__ __forceinline__ float4 ln_apply(float4 u, float mean, float rstd, float4 gm, float4 bt) {
-    return make_float4((u.x - mean) * rstd * gm.x + bt.x, (u.y - mean) * rstd * gm.y + bt.y, (u.z - mean) * rstd * gm.z + bt.z,
-                       (u.w - mean) * rstd * gm.w + bt.w);
+// the FFN block's view of the layer: dense_1, dense_2, the intermediate LayerNorm; the filter LayerNorm made its input
+__device__ __forceinline__ FfnWeights ffn_weights(const dr4sr_fmlp_layer_weights& w) {
+    return {w.dense_1_weight, w.dense_1_bias, w.dense_2_weight, w.dense_2_bias, w.inter_ln_weight, w.inter_ln_bias, w.filter_ln_weight,
+            w.filter_ln_bias};
 }
 // the sequence tile twice: x[(l - r) mod L] = X2[l - r + L]
 __device__ __forceinline__ void load_twice(float* __restrict__ X2, const float* __restrict__ xb, int L) {
@@ -92,9 +95,11 @@ __global__ __launch_bounds__(256) void k_fmlp_layer_fwd(const Args a) {
     const bool drop = a.p > 0.f;
     const uint32_t s_filt = FOP_SITE_FILT(a.layer), s_ffn = FOP_SITE_FFN(a.layer);
     const int64_t SS = saved_stride(L);
+    const FfnWeights fw = ffn_weights(a.w);
     for (int i = tid; i < L * (D / 4); i += 256) st4(ML + 4 * i, ld4(a.m + 4 * i));
 
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
+        const uint64_t t0 = (uint64_t)b * L;                   // the sequence's first token
         float* sv = a.saved ? a.saved + (size_t)b * SS : nullptr;
         float *sv_uf = sv, *sv_h = sv + (size_t)L * D, *sv_u2 = sv_h + (size_t)L * F;
         load_twice(X2, a.x + (size_t)b * L * D, L);
@@ -125,43 +130,8 @@ __global__ __launch_bounds__(256) void k_fmlp_layer_fwd(const Args a) {
             }
         }
         __syncthreads();                                       // every read of X2 is done: R is free
-        // ---- FFN
-        {
-            f32x16 hacc[F / 64];
-            acc_zero(hacc);
-            mma_64xN<D, F / 64>(As, LDX, a.w.dense_1_weight, hacc);
-            acc_to_lds<F / 64>(hacc, R, LDF, a.w.dense_1_bias);
-        }
-        __syncthreads();
-        for (int i = tid; i < 64 * (F / 4); i += 256) {
-            const int row = i / (F / 4), cc = (i % (F / 4)) * 4;
-            float4 hv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < L) {
-                hv = ld4(R + row * LDF + cc);
-                if (sv) st4(sv_h + (size_t)row * F + cc, hv);
-                hv = make_float4(gelu_erf(hv.x), gelu_erf(hv.y), gelu_erf(hv.z), gelu_erf(hv.w));
-            }
-            st4(R + row * LDF + cc, hv);
-        }
-        __syncthreads();
-        {
-            f32x16 oacc[1];
-            acc_zero(oacc);
-            mma_64xN<F, 1>(R, LDF, a.w.dense_2_weight, oacc);
-            acc_to_lds<1>(oacc, Bs, LDX, a.w.dense_2_bias);
-        }
-        __syncthreads();
-        // ---- u2 = xf + drop(o), y = LN_i(u2): 16 lanes per row
-        for (int row = tid >> 4; row < L; row += 16) {
-            const int cc = 4 * (tid & 15);
-            float4 o = ld4(Bs + row * LDX + cc);
-            if (drop) o = mul4(o, drop4(rk, s_ffn, ((uint64_t)b * L + row) * D + cc));
-            float4 u[1] = {add4(ld4(As + row * LDX + cc), o)};
-            if (sv) st4(sv_u2 + (size_t)row * D + cc, u[0]);
-            float mean, rstd;
-            ln_stats16<1>(u, mean, rstd, a.eps);
-            st4(a.y + ((size_t)b * L + row) * D + cc, ln_apply(u[0], mean, rstd, ld4(a.w.inter_ln_weight + cc), ld4(a.w.inter_ln_bias + cc)));
-        }
+        // ---- FFN, y = LN_i(xf + drop(o))
+        ffn_fwd<D, F, false>(As, Bs, LDX, R, LDF, fw, sv ? sv_h : nullptr, sv ? sv_u2 : nullptr, a.y + t0 * D, rk, drop, 0u, s_ffn, t0, L, a.eps);
         __syncthreads();
     }
 }
@@ -182,8 +152,9 @@ __global__ __launch_bounds__(256) void k_fmlp_layer_bwd(const Args a) {
     const bool drop = a.p > 0.f;
     const uint32_t s_filt = FOP_SITE_FILT(a.layer), s_ffn = FOP_SITE_FFN(a.layer);
     const int64_t SS = saved_stride(L);
-    const int lane = tid & 63, wv = tid >> 6, r32 = lane & 31, g32 = lane >> 5, rh = wv & 1, cg = wv >> 1;
     float* ws = a.slots + (size_t)blockIdx.x * NW;
+    const FfnWeights fw = ffn_weights(a.w);
+    const FfnGrads fg = {ws + O_W1, ws + O_B1, ws + O_W2, ws + O_B2, ws + O_ILNW, ws + O_ILNB};
     for (int i = tid; i < L * (D / 4); i += 256) st4(ML + 4 * i, ld4(a.m + 4 * i));
     float4 dmacc[4];                       // this thread's taps r = l0 .. l0 + 3 of dm, summed over the workgroup's sequences in order
 #pragma unroll
@@ -191,88 +162,12 @@ __global__ __launch_bounds__(256) void k_fmlp_layer_bwd(const Args a) {
 
     for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
         const bool first = b == (int64_t)blockIdx.x;
+        const uint64_t t0 = (uint64_t)b * L;                   // the sequence's first token
         const float* sv = a.saved + (size_t)b * SS;
         const float *sv_uf = sv, *sv_h = sv + (size_t)L * D, *sv_u2 = sv_h + (size_t)L * F;
         // ---------------------------------------------------------------- A: the intermediate LayerNorm and the FFN
-        load_rows<D>(As, LDX, a.dy + (size_t)b * L * D, D, L);
-        load_rows<D>(Bs, LDX, sv_u2, D, L);
-        __syncthreads();
-        ln_stats_rows<D>(Bs, LDX, st2, L, a.eps);
-        __syncthreads();
-        ln_affine_grads<D>(ws + O_ILNW, ws + O_ILNB, As, Bs, LDX, st2, L, first);
-        __syncthreads();
-        // du2 -> As, d f2 = du2 * mask -> Bs
-        for (int row = tid >> 4; row < 64; row += 16) {
-            const int cc = 4 * (tid & 15);
-            float4 dz[1] = {ld4(As + row * LDX + cc)}, u[1] = {ld4(Bs + row * LDX + cc)}, gm[1] = {ld4(a.w.inter_ln_weight + cc)};
-            float4 dg[1] = {make_float4(0.f, 0.f, 0.f, 0.f)}, db[1] = {make_float4(0.f, 0.f, 0.f, 0.f)};
-            ln_bwd_row<1>(dz, u, st2[2 * row], st2[2 * row + 1], gm, dg, db);
-            st4(As + row * LDX + cc, dz[0]);
-            float4 df = dz[0];
-            if (drop && row < L) df = mul4(df, drop4(rk, s_ffn, ((uint64_t)b * L + row) * D + cc));
-            st4(Bs + row * LDX + cc, df);
-        }
-        // h = gelu(hpre) -> R
-        for (int i = tid; i < 64 * (F / 4); i += 256) {
-            const int row = i / (F / 4), cc = (i % (F / 4)) * 4;
-            float4 hv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < L) {
-                hv = ld4(sv_h + (size_t)row * F + cc);
-                hv = make_float4(gelu_erf(hv.x), gelu_erf(hv.y), gelu_erf(hv.z), gelu_erf(hv.w));
-            }
-            st4(R + row * LDF + cc, hv);
-        }
-        __syncthreads();
-        wgrad_tn<D, F>(ws + O_W2, F, Bs, LDX, R, LDF, first);
-        colsum(ws + O_B2, Bs, LDX, D, L, first);
-        __syncthreads();
-        // R := gelu'(hpre); then d hpre = (d f2 W2) * R in place
-        for (int i = tid; i < 64 * (F / 4); i += 256) {
-            const int row = i / (F / 4), cc = (i % (F / 4)) * 4;
-            float4 fv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < L) {
-                const float4 hv = ld4(sv_h + (size_t)row * F + cc);
-                fv = make_float4(gelu_erf_grad(hv.x), gelu_erf_grad(hv.y), gelu_erf_grad(hv.z), gelu_erf_grad(hv.w));
-            }
-            st4(R + row * LDF + cc, fv);
-        }
-        {
-            f32x16 acc[F / 64];
-            acc_zero(acc);
-            mma_wT<D, F / 64>(Bs, LDX, a.w.dense_2_weight, F, acc);
-            __syncthreads();                                   // the factor is in R, every wave is done reading d f2 from Bs
-#pragma unroll
-            for (int i = 0; i < F / 64; ++i)
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    float* pp = R + (rh * 32 + (q & 3) + 8 * (q >> 2) + 4 * g32) * LDF + (cg + 2 * i) * 32 + r32;
-                    *pp *= acc[i][q];
-                }
-        }
-        // xf = LN_f(uf) -> Bs, statistics -> st1
-        for (int row = tid >> 4; row < 64; row += 16) {
-            const int cc = 4 * (tid & 15);
-            float4 u[1] = {row < L ? ld4(sv_uf + (size_t)row * D + cc) : make_float4(0.f, 0.f, 0.f, 0.f)};
-            float mean, rstd;
-            ln_stats16<1>(u, mean, rstd, a.eps);
-            if ((tid & 15) == 0) { st1[2 * row] = row < L ? mean : 0.f; st1[2 * row + 1] = row < L ? rstd : 0.f; }
-            float4 xf = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < L) xf = ln_apply(u[0], mean, rstd, ld4(a.w.filter_ln_weight + cc), ld4(a.w.filter_ln_bias + cc));
-            st4(Bs + row * LDX + cc, xf);
-        }
-        __syncthreads();
-        wgrad_tn<F, D>(ws + O_W1, D, R, LDF, Bs, LDX, first);
-        colsum(ws + O_B1, R, LDF, F, L, first);
-        {
-            f32x16 acc[1];
-            acc_zero(acc);
-            mma_wT<F, 1>(R, LDF, a.w.dense_1_weight, D, acc);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                float* pp = As + (rh * 32 + (q & 3) + 8 * (q >> 2) + 4 * g32) * LDX + cg * 32 + r32;
-                *pp += acc[0][q];                               // d xf = d hpre W1 + du2
-            }
-        }
+        ffn_ln_bwd<D, F, false>(As, Bs, LDX, R, LDF, st1, st2, fw, sv_uf, sv_h, sv_u2, a.dy + t0 * D, fg, rk, drop, 0u, s_ffn, t0, L, a.eps,
+                                first);                // d xf -> As
         __syncthreads();                                       // every read of R is done: X2 | DY2 take it over
         // ---------------------------------------------------------------- B: the filter LayerNorm and the filter
         load_rows<D>(Bs, LDX, sv_uf, D, L);
@@ -324,8 +219,10 @@ __global__ __launch_bounds__(256) void k_fmlp_layer_bwd(const Args a) {
 // Sums the workgroups' partial slots in index order and writes the 9 gradients.  The first FOLD_BLOCKS blocks take four features of dm
 // each: thread (r, j) sums tap r of feature 4 blockIdx.x + j over the slots, then one (k, j) pair per thread folds the column back,
 //     d Wre[k][d] = (c_k / L) sum_r cos(2 pi k r / L) dm[r][d],    d Wim[k][d] = -(c_k / L) sum_r sin(2 pi k r / L) dm[r][d]
-// (fmlp_coef_bwd_job of linear.hip, stored instead of added).  The other blocks: one element of the eight remaining tensors per thread.
-__global__ __launch_bounds__(256) void k_fmlp_layer_reduce(const float* __restrict__ slots, int n_slots, int L, dr4sr_fmlp_layer_grads dw) {
+// (fmlp_coef_bwd_job of linear.hip, stored instead of added).  The other blocks: one element of the eight remaining tensors (`rest`) per
+// thread.
+__global__ __launch_bounds__(256) void k_fmlp_layer_reduce(const float* __restrict__ slots, int n_slots, int L, float* __restrict__ dcw,
+                                                           ReduceTable rest) {
     if ((int)blockIdx.x < FOLD_BLOCKS) {
         __shared__ float ct[64], sn[64], dm[64 * 4];
         const int r = threadIdx.x >> 2, j = threadIdx.x & 3, d0 = 4 * blockIdx.x;
@@ -343,24 +240,12 @@ __global__ __launch_bounds__(256) void k_fmlp_layer_reduce(const float* __restri
                 gi -= sn[t] * v;
             }
             const float cf = ((k == 0 || 2 * k == L) ? 1.f : 2.f) / (float)L;
-            dw.complex_weight[(k * D + d0 + jj) * 2] = cf * gr;
-            dw.complex_weight[(k * D + d0 + jj) * 2 + 1] = cf * gi;
+            dcw[(k * D + d0 + jj) * 2] = cf * gr;
+            dcw[(k * D + d0 + jj) * 2 + 1] = cf * gi;
         }
         return;
     }
-    const int e = O_FLNW + ((int)blockIdx.x - FOLD_BLOCKS) * 256 + (int)threadIdx.x;
-    if (e >= NW) return;
-    const float s = det_sum(slots + e, n_slots, NW);
-    float* dst; int o;
-    if (e < O_FLNB) { dst = dw.filter_ln_weight; o = O_FLNW; }
-    else if (e < O_W1) { dst = dw.filter_ln_bias; o = O_FLNB; }
-    else if (e < O_B1) { dst = dw.dense_1_weight; o = O_W1; }
-    else if (e < O_W2) { dst = dw.dense_1_bias; o = O_B1; }
-    else if (e < O_B2) { dst = dw.dense_2_weight; o = O_W2; }
-    else if (e < O_ILNW) { dst = dw.dense_2_bias; o = O_B2; }
-    else if (e < O_ILNB) { dst = dw.inter_ln_weight; o = O_ILNW; }
-    else { dst = dw.inter_ln_bias; o = O_ILNB; }
-    dst[e - o] = s;
+    reduce_store(slots, n_slots, NW, O_FLNW + ((int)blockIdx.x - FOLD_BLOCKS) * 256 + (int)threadIdx.x, rest);
 }
 
 // =================================================================================================================== LayerNorm op
@@ -458,30 +343,14 @@ __global__ __launch_bounds__(256) void k_ln_bwd(const float* __restrict__ x, con
         slots[(size_t)blockIdx.x * 2 * Dn + i] = ((lds[i] + lds[2 * Dn + i]) + lds[4 * Dn + i]) + lds[6 * Dn + i];
 }
 
-__global__ void k_ln_reduce(const float* __restrict__ slots, int n_slots, int Dn, float* __restrict__ dw, float* __restrict__ db) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= 2 * Dn) return;
-    const float s = det_sum(slots + e, n_slots, (size_t)2 * Dn);
-    if (e < Dn) dw[e] = s; else db[e - Dn] = s;
-}
-
 // =================================================================================================================== host
 static int shape_check(int64_t B, int L, int Dn, int Fn) {
     if (B < 0) return DR4SR_E_ARG;
     if (Dn != D || Fn != F || L < 2 || L > 64 || (L & 1)) return DR4SR_E_SHAPE;
     return 0;
 }
-static int n_slots(int64_t B) { return B < MAX_SLOTS ? (int)B : MAX_SLOTS; }
 static int64_t ws_bytes_of(int64_t B, int backward) {
     return ((int64_t)M_FLOATS + (backward ? (int64_t)n_slots(B) * NW : 0)) * (int64_t)sizeof(float);
-}
-static bool weights_ok(const dr4sr_fmlp_layer_weights* w) {
-    return w && w->complex_weight && w->filter_ln_weight && w->filter_ln_bias && w->dense_1_weight && w->dense_1_bias && w->dense_2_weight &&
-           w->dense_2_bias && w->inter_ln_weight && w->inter_ln_bias;
-}
-static bool grads_ok(const dr4sr_fmlp_layer_grads* w) {
-    return w && w->complex_weight && w->filter_ln_weight && w->filter_ln_bias && w->dense_1_weight && w->dense_1_bias && w->dense_2_weight &&
-           w->dense_2_bias && w->inter_ln_weight && w->inter_ln_bias;
 }
 static int launch_coef(const float* cw, float* m, int L, hipStream_t st) {
     hipLaunchKernelGGL(k_fmlp_op_coef, dim3((L * D + 255) / 256), dim3(256), 0, st, cw, m, L);
@@ -514,7 +383,7 @@ extern "C" int64_t dr4sr_fmlp_layer_workspace_bytes(int64_t B, int32_t L, int32_
 extern "C" int dr4sr_fmlp_layer_fwd(const float* x, const dr4sr_fmlp_layer_weights* w, int64_t B, int32_t L, int32_t D, int32_t F, float eps,
                                     float p_drop, uint64_t seed, uint32_t step, int32_t layer, float* y, float* saved, void* ws,
                                     int64_t ws_bytes, void* stream) {
-    if (!fop::weights_ok(w) || layer < 0 || layer > 1024 || !(p_drop >= 0.f && p_drop < 1.f) || !(eps >= 0.f)) return DR4SR_E_ARG;
+    if (!fop::all_set<9>(w) || !fop::layer_args_ok(layer, p_drop, eps)) return DR4SR_E_ARG;
     const int rc = fop::shape_check(B, L, D, F);
     if (rc) return rc;
     if (B == 0) return 0;                                      // (an empty tensor's pointer may be null)
@@ -535,8 +404,7 @@ extern "C" int dr4sr_fmlp_layer_fwd(const float* x, const dr4sr_fmlp_layer_weigh
 extern "C" int dr4sr_fmlp_layer_bwd(const float* x, const dr4sr_fmlp_layer_weights* w, int64_t B, int32_t L, int32_t D, int32_t F, float eps,
                                     float p_drop, uint64_t seed, uint32_t step, int32_t layer, const float* saved, const float* dy, float* dx,
                                     const dr4sr_fmlp_layer_grads* dw, void* ws, int64_t ws_bytes, void* stream) {
-    if (!fop::weights_ok(w) || !fop::grads_ok(dw) || layer < 0 || layer > 1024 || !(p_drop >= 0.f && p_drop < 1.f) || !(eps >= 0.f))
-        return DR4SR_E_ARG;
+    if (!fop::all_set<9>(w) || !fop::all_set<9>(dw) || !fop::layer_args_ok(layer, p_drop, eps)) return DR4SR_E_ARG;
     const int rc = fop::shape_check(B, L, D, F);
     if (rc) return rc;
     if (B > 0 && (!x || !saved || !dy || !dx)) return DR4SR_E_ARG;
@@ -544,14 +412,10 @@ extern "C" int dr4sr_fmlp_layer_bwd(const float* x, const dr4sr_fmlp_layer_weigh
     hipStream_t st = (hipStream_t)stream;
     if (B == 0) {                                              // no sequence: the gradients of the weights are zeros
         const dr4sr_fmlp_layer_grads& g = *dw;
-        float* t[9] = {g.complex_weight, g.filter_ln_weight, g.filter_ln_bias, g.dense_1_weight, g.dense_1_bias, g.dense_2_weight,
-                       g.dense_2_bias, g.inter_ln_weight, g.inter_ln_bias};
-        const int64_t n[9] = {(int64_t)(L / 2 + 1) * D * 2, D, D, (int64_t)F * D, F, (int64_t)D * F, D, D, D};
-        for (int i = 0; i < 9; ++i) {
-            const int e = hip_ret(hipMemsetAsync(t[i], 0, n[i] * sizeof(float), st));
-            if (e) return e;
-        }
-        return 0;
+        const fop::ZeroSpan t[9] = {{g.complex_weight, (int64_t)(L / 2 + 1) * D * 2}, {g.filter_ln_weight, D}, {g.filter_ln_bias, D},
+                                    {g.dense_1_weight, (int64_t)F * D}, {g.dense_1_bias, F}, {g.dense_2_weight, (int64_t)D * F},
+                                    {g.dense_2_bias, D}, {g.inter_ln_weight, D}, {g.inter_ln_bias, D}};
+        return fop::zero_fill(t, 9, st);
     }
     float* m = (float*)ws;
     int e = fop::launch_coef(w->complex_weight, m, L, st);
@@ -565,8 +429,12 @@ extern "C" int dr4sr_fmlp_layer_bwd(const float* x, const dr4sr_fmlp_layer_weigh
     hipLaunchKernelGGL(fop::k_fmlp_layer_bwd, dim3(ns), dim3(256), lds, st, a);
     e = DR4SR_LAUNCH_CHECK();
     if (e) return e;
-    hipLaunchKernelGGL(fop::k_fmlp_layer_reduce, dim3(fop::FOLD_BLOCKS + (fop::NW - fop::O_FLNW + 255) / 256), dim3(256), 0, st, a.slots, ns, L,
-                       *dw);
+    using namespace fop;
+    const int off[9] = {O_FLNW, O_FLNB, O_W1, O_B1, O_W2, O_B2, O_ILNW, O_ILNB, NW};
+    float* dst[9];
+    memcpy(dst, dw, sizeof dst);                               // complex_weight, then the eight gradients in the slot's order
+    hipLaunchKernelGGL(k_fmlp_layer_reduce, dim3(FOLD_BLOCKS + (NW - O_FLNW + 255) / 256), dim3(256), 0, st, a.slots, ns, L, dst[0],
+                       reduce_table(dst + 1, off, 8));
     return DR4SR_LAUNCH_CHECK();
 }
 
@@ -595,9 +463,8 @@ extern "C" int dr4sr_layer_norm_bwd(const float* x, const float* weight, int64_t
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (n_rows == 0) {
-        int e = hip_ret(hipMemsetAsync(dw, 0, D * sizeof(float), st));
-        if (!e) e = hip_ret(hipMemsetAsync(db, 0, D * sizeof(float), st));
-        return e;
+        const fop::ZeroSpan t[2] = {{dw, D}, {db, D}};
+        return fop::zero_fill(t, 2, st);
     }
     if (!x || !dy || !dx) return DR4SR_E_ARG;
     const int ns = fop::ln_slots(n_rows);
@@ -605,6 +472,8 @@ extern "C" int dr4sr_layer_norm_bwd(const float* x, const float* weight, int64_t
     hipLaunchKernelGGL(fop::k_ln_bwd, dim3(ns), dim3(256), (size_t)8 * D * sizeof(float), st, x, weight, dy, n_rows, D, eps, dx, (float*)ws);
     int e = DR4SR_LAUNCH_CHECK();
     if (e) return e;
-    hipLaunchKernelGGL(fop::k_ln_reduce, dim3((2 * D + 255) / 256), dim3(256), 0, st, (const float*)ws, ns, D, dw, db);
+    float* dst[2] = {dw, db};
+    const int off[3] = {0, D, 2 * D};
+    hipLaunchKernelGGL(fop::k_slot_reduce, dim3((2 * D + 255) / 256), dim3(256), 0, st, (const float*)ws, ns, 2 * D, fop::reduce_table(dst, off, 2));
     return DR4SR_LAUNCH_CHECK();
 }
