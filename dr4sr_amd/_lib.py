@@ -382,6 +382,13 @@ SYMBOLS = {
     "dr4sr_layer_norm_fwd": (C.c_int, [_f32p, _f32p, _f32p, C.c_int64, C.c_int32, C.c_float, _f32p, C.c_void_p]),
     "dr4sr_layer_norm_bwd": (C.c_int, [_f32p, _f32p, C.c_int64, C.c_int32, C.c_float, _f32p, _f32p, _f32p, _f32p, C.c_void_p, C.c_int64,
                                        C.c_void_p]),
+    # additive to ABI 10: the stateless GRU layer op on dense tensors (csrc/gru_op.hip)
+    "dr4sr_gru_layer_saved_floats": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "dr4sr_gru_layer_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "dr4sr_gru_layer_fwd": (C.c_int, [_f32p, _f32p, _f32p, _i64p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _f32p, _f32p, C.c_void_p,
+                                      C.c_int64, C.c_void_p]),
+    "dr4sr_gru_layer_bwd": (C.c_int, [_f32p, _f32p, _f32p, _i64p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _f32p, _f32p, _f32p, _f32p,
+                                      _f32p, _f32p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 _lib = None
@@ -397,7 +404,8 @@ _AFTER_PARENT_AB = ("dr4sr_sasrec_encode_w", "dr4sr_sasrec_encode_w_bwd", "dr4sr
                     "dr4sr_sasrec_layer_saved_floats", "dr4sr_sasrec_layer_workspace_bytes", "dr4sr_sasrec_layer_fwd", "dr4sr_sasrec_layer_bwd",
                     "dr4sr_seq_pool_fwd", "dr4sr_seq_pool_bwd", "dr4sr_dropout_apply", "dr4sr_embed_gather_posadd_bwd",
                     "dr4sr_fmlp_layer_saved_floats", "dr4sr_fmlp_layer_workspace_bytes", "dr4sr_fmlp_layer_fwd", "dr4sr_fmlp_layer_bwd",
-                    "dr4sr_layer_norm_workspace_bytes", "dr4sr_layer_norm_fwd", "dr4sr_layer_norm_bwd")
+                    "dr4sr_layer_norm_workspace_bytes", "dr4sr_layer_norm_fwd", "dr4sr_layer_norm_bwd",
+                    "dr4sr_gru_layer_saved_floats", "dr4sr_gru_layer_workspace_bytes", "dr4sr_gru_layer_fwd", "dr4sr_gru_layer_bwd")
 
 
 def load():

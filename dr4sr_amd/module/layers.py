@@ -17,11 +17,20 @@ FMLPEncoderOps / FMLPOps — the reference's FMLPEncoder (module/layers.py:740-8
 written the same way: each `Layer` (FilterLayer + Intermediate) is one torch.ops.dr4sr_hip.fmlp_layer (csrc/fmlp_op.hip), the embedding
 LayerNorm torch.ops.dr4sr_hip.layer_norm.  Parameters carry the reference's names, so a checkpoint of the engine-backed FMLP loads with
 strict=True (its `item_embedding.weight` is the table the module is handed).  The dropout sites are the FMLP engine's: 0 for the
-embedding, 1 + 2 l and 2 + 2 l for layer l; the step counter works as above."""
+embedding, 1 + 2 l and 2 + 2 l for layer l; the step counter works as above.
+
+GRULayerOps / GRU4RecQueryEncoderOps — the reference's GRULayer (module/layers.py:117-136) and the query encoder of its GRU4Rec
+(model/gru4rec.py:12-34) written the same way: every GRU layer is one torch.ops.dr4sr_hip.gru_layer (csrc/gru_op.hip).  The op takes an
+optional `seqlen`: without it every one of the L steps is computed, as torch.nn.GRU does on the padded batch; with it the steps behind
+each length are skipped and come out as zeros, which changes nothing that 'origin' or 'last' pooling reads.  The H -> D projection
+behind the GRU is the reference's own nn.Linear outside GRULayer and stays torch's (F.linear)."""
 from __future__ import annotations
+
+import math
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import _lib
 from .. import ops  # noqa: F401  (registers torch.ops.dr4sr_hip.*)
@@ -198,3 +207,69 @@ class FMLPOps(nn.Module):
         if self.training:
             self.step += 1
         return x[:, -1] if need_pooling else x
+
+
+class _GRUWeights(nn.Module):
+    """the parameters of torch.nn.GRU(bias=False), same names, same shapes, same initialisation (uniform in +-1 / sqrt(hidden))"""
+    def __init__(self, input_dim, hidden, num_layer):
+        super().__init__()
+        k = 1.0 / math.sqrt(hidden)
+        for l in range(num_layer):
+            self.register_parameter(f"weight_ih_l{l}", nn.Parameter(torch.empty(3 * hidden, input_dim if l == 0 else hidden).uniform_(-k, k)))
+            self.register_parameter(f"weight_hh_l{l}", nn.Parameter(torch.empty(3 * hidden, hidden).uniform_(-k, k)))
+
+
+class GRULayerOps(nn.Module):
+    """GRULayer (module/layers.py:117-136): `num_layer` GRU layers without biases, h_0 = 0, on input [B, L, input_dim].
+    forward(input, seqlen=None) -> out [B, L, output_dim], or (out, hidden [num_layer, B, output_dim]) with return_hidden, hidden being each
+    layer's output at its last computed step (L - 1 without seqlen, seqlen - 1 with it; zeros for an empty sequence)"""
+    def __init__(self, input_dim, output_dim, num_layer=1, bias=False, batch_first=True, bidirectional=False, return_hidden=False) -> None:
+        super().__init__()
+        for given, name in ((bias, "bias=True"), (not batch_first, "batch_first=False"), (bidirectional, "bidirectional=True")):
+            if given:
+                raise NotImplementedError(f"{name}: torch.ops.dr4sr_hip.gru_layer computes a forward-direction GRU without biases on "
+                                          "[B, L, I] input (bias=False, batch_first=True, bidirectional=False)")
+        self.gru = _GRUWeights(input_dim, output_dim, num_layer)
+        self.num_layer, self.return_hidden = int(num_layer), return_hidden
+
+    def forward(self, input, seqlen=None):
+        o = torch.ops.dr4sr_hip
+        if seqlen is not None:
+            seqlen = seqlen.contiguous().view(-1).to(torch.int64)
+        x, hidden = input.contiguous(), []
+        for l in range(self.num_layer):
+            x, _ = o.gru_layer(x, getattr(self.gru, f"weight_ih_l{l}"), getattr(self.gru, f"weight_hh_l{l}"), seqlen)
+            if self.return_hidden:
+                hidden.append(x[:, -1] if seqlen is None else o.seq_pool(x, seqlen, _lib.POOL_LAST))
+        return (x, torch.stack(hidden)) if self.return_hidden else x
+
+
+class GRU4RecQueryEncoderOps(nn.Module):
+    """the query encoder of the reference's GRU4Rec (model/gru4rec.py:12-34) on `item_embedding` (an nn.Embedding the caller owns).  The
+    children carry the names the reference's VStackLayer(Sequential(Lambda, table, Dropout, GRULayer), Linear) gives them, so the
+    state-dict keys are 0.1.weight, 0.3.gru.weight_{ih,hh}_l{k}, 1.weight and 1.bias: a GRU4Rec checkpoint loads with the `query_encoder.`
+    prefix stripped.  use_seqlen hands batch['seqlen'] to the GRU layers (the pads are skipped); False computes them as the reference does"""
+    def __init__(self, fiid, item_embedding, hidden_size, layer_num, dropout, max_seq_len, seed: int = 2023, use_seqlen: bool = True) -> None:
+        super().__init__()
+        D = item_embedding.weight.shape[1]
+        self.fiid, self.p_drop, self.use_seqlen = fiid, float(dropout), bool(use_seqlen)
+        self.add_module("0", nn.ModuleDict({"1": item_embedding, "3": GRULayerOps(D, hidden_size, layer_num)}))
+        self.add_module("1", nn.Linear(hidden_size, D))
+        # E[idx] + 0 is the gather: embed_gather_posadd with a zero position table keeps the table scatter of the backward in HIP
+        self.register_buffer("zero_pos", torch.zeros(max_seq_len, D), persistent=False)
+        self.seed, self.step = int(seed), 0
+
+    def forward(self, batch, need_pooling=True):
+        o = torch.ops.dr4sr_hip
+        inner, proj = self._modules["0"], self._modules["1"]
+        p = self.p_drop if self.training else 0.0
+        x = o.embed_gather_posadd(inner["1"].weight, self.zero_pos, batch["in_" + self.fiid])     # gru4rec.py:15-16
+        if p > 0.0:                                                                                # gru4rec.py:17
+            x = o.dropout(x, p, self.seed, self.step, _lib.SITE_EMB)
+        x = inner["3"](x, batch["seqlen"] if self.use_seqlen else None)                            # gru4rec.py:18
+        x = F.linear(x, proj.weight, proj.bias)                                                    # gru4rec.py:20 (torch's own)
+        if self.training:
+            self.step += 1
+        if not need_pooling:
+            return x
+        return o.seq_pool(x, batch["seqlen"], _lib.POOL_ORIGIN if self.training else _lib.POOL_LAST)   # gru4rec.py:28-32

@@ -23,8 +23,11 @@ a reference-style model written against plain torch ops:
                eps, p_drop, seed, step, layer) -> (y, saved)  one FMLP Layer (FilterLayer + Intermediate) of module/layers.py:740-791 on dense
                                                               [B, L, 64] (autograd: d x and the 9 weight gradients, bit-reproducible)
     layer_norm(x, weight, bias, eps) -> y                     nn.LayerNorm over the last dimension: model/fmlp.py:25 (autograd: d x, d w, d b)
-    (+ embed_gather_posadd_backward, sasrec_layer_backward, seq_pool_backward, fmlp_layer_backward, layer_norm_backward: the autograd
-     formulas, ops themselves)
+    gru_layer(x, weight_ih, weight_hh, seqlen?) -> (y, saved)   one layer of nn.GRU(bias=False, batch_first=True), module/layers.py:117-136, on
+                                                              dense [B, L, I]; seqlen skips the steps behind each length (autograd: d x,
+                                                              d weight_ih, d weight_hh, bit-reproducible)
+    (+ embed_gather_posadd_backward, sasrec_layer_backward, seq_pool_backward, fmlp_layer_backward, layer_norm_backward,
+     gru_layer_backward: the autograd formulas, ops themselves)
 
 Every implementation only enqueues HIP kernels of libdr4sr_hip.so on the current stream; there is no CPU kernel (the ops raise on
 CPU tensors).  The encoder LAYER is a dispatcher op: stateless, dense tensors in and out, its dropout keyed by explicit (seed, step,
@@ -642,7 +645,97 @@ def _ln_backward(ctx, g):
 layer_norm.register_autograd(_ln_backward, setup_context=_ln_setup)
 
 
+# ------------------------------------------------------------------------------------------------ GRU layer
+def _gru_dims(x, weight_ih, weight_hh, seqlen, *more):
+    """(B, L, I, H, saved floats) of a gru_layer call; every refusal (device, dtype, contiguity, shape) is raised here, before a launch"""
+    _need_cuda(x, weight_ih, weight_hh, seqlen, *more)
+    for name, t in (("x", x), ("weight_ih", weight_ih), ("weight_hh", weight_hh)) + tuple(("tensor", m) for m in more):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.Dr4srError(f"gru_layer: {name} must be a contiguous float32 tensor")
+    if x.dim() != 3 or weight_ih.dim() != 2 or weight_hh.dim() != 2:
+        raise _lib.Dr4srError("gru_layer: x must be [B, L, I], weight_ih [3H, I] and weight_hh [3H, H]")
+    B, L, I = (int(s) for s in x.shape)
+    H = int(weight_hh.shape[1])
+    if tuple(weight_ih.shape) != (3 * H, I) or tuple(weight_hh.shape) != (3 * H, H):
+        raise _lib.Dr4srError(f"gru_layer: weight_ih must be [3H, I] = {(3 * H, I)} and weight_hh [3H, H] = {(3 * H, H)}, got "
+                              f"{tuple(weight_ih.shape)} and {tuple(weight_hh.shape)}")
+    if seqlen is not None and (seqlen.dtype != torch.int64 or tuple(seqlen.shape) != (B,) or not seqlen.is_contiguous()):
+        raise _lib.Dr4srError("gru_layer: seqlen must be a contiguous int64 tensor [B] (or None: every sequence has L steps)")
+    n = int(_lib.load().dr4sr_gru_layer_saved_floats(B, L, I, H))          # the shape refusals (DR4SR_E_SHAPE)
+    _lib.check(min(n, 0), "dr4sr_gru_layer_saved_floats")
+    return B, L, I, H, n
+
+
+def _gru_ws(lib, B, L, I, H, backward, device):
+    nb = int(lib.dr4sr_gru_layer_workspace_bytes(B, L, I, H, backward))
+    _lib.check(min(nb, 0), "dr4sr_gru_layer_workspace_bytes")
+    return torch.empty(max(nb // 4, 1), dtype=torch.float32, device=device), nb
+
+
+@torch.library.custom_op(f"{NS}::gru_layer", mutates_args=())
+def gru_layer(x: torch.Tensor, weight_ih: torch.Tensor, weight_hh: torch.Tensor,
+              seqlen: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """one layer of torch.nn.GRU(bias=False, batch_first=True) (module/layers.py:117-136) on x [B, L, I], h_0 = 0: I in {64, 128, 256},
+    H in {128, 256}, L <= 1024.  seqlen None computes every step (the reference); with seqlen [B] int64 the steps at and behind
+    seqlen[b] are skipped and y is 0 there.  -> (y [B, L, H], saved: the opaque buffer the backward reads)"""
+    B, L, I, H, n = _gru_dims(x, weight_ih, weight_hh, seqlen)
+    lib = _lib.load()
+    y = torch.empty(B, L, H, dtype=torch.float32, device=x.device)
+    saved = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
+    ws, nb = _gru_ws(lib, B, L, I, H, 0, x.device)
+    _lib.check(lib.dr4sr_gru_layer_fwd(_lib.ptr(x), _lib.ptr(weight_ih), _lib.ptr(weight_hh), _lib.ptr(seqlen), B, L, I, H, _lib.ptr(y),
+                                       _lib.ptr(saved), _lib.ptr(ws), nb, _lib.cur_stream()), "dr4sr_gru_layer_fwd")
+    return y, saved
+
+
+@gru_layer.register_fake
+def _(x, weight_ih, weight_hh, seqlen):
+    B, L, _ = x.shape
+    H = weight_hh.shape[1]
+    return x.new_empty(B, L, H), x.new_empty(max(B * L * 4 * H, 1))
+
+
+@torch.library.custom_op(f"{NS}::gru_layer_backward", mutates_args=())
+def gru_layer_backward(x: torch.Tensor, weight_ih: torch.Tensor, weight_hh: torch.Tensor, seqlen: Optional[torch.Tensor], y: torch.Tensor,
+                       saved: torch.Tensor, dy: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (dx, d weight_ih, d weight_hh); written, not accumulated; bit-reproducible.  dy behind seqlen is not read"""
+    dyc = dy.contiguous().float()
+    B, L, I, H, n = _gru_dims(x, weight_ih, weight_hh, seqlen, y, saved, dyc)
+    if tuple(y.shape) != (B, L, H) or tuple(dyc.shape) != (B, L, H) or saved.numel() < n:
+        raise _lib.Dr4srError("gru_layer_backward: y and dy must be [B, L, H], saved the forward's")
+    lib = _lib.load()
+    dx, dw_ih, dw_hh = torch.empty_like(x), torch.empty_like(weight_ih), torch.empty_like(weight_hh)
+    ws, nb = _gru_ws(lib, B, L, I, H, 1, x.device)
+    _lib.check(lib.dr4sr_gru_layer_bwd(_lib.ptr(x), _lib.ptr(weight_ih), _lib.ptr(weight_hh), _lib.ptr(seqlen), B, L, I, H, _lib.ptr(y),
+                                       _lib.ptr(saved), _lib.ptr(dyc), _lib.ptr(dx), _lib.ptr(dw_ih), _lib.ptr(dw_hh), _lib.ptr(ws), nb,
+                                       _lib.cur_stream()), "dr4sr_gru_layer_bwd")
+    return dx, dw_ih, dw_hh
+
+
+@gru_layer_backward.register_fake
+def _(x, weight_ih, weight_hh, seqlen, y, saved, dy):
+    return torch.empty_like(x), torch.empty_like(weight_ih), torch.empty_like(weight_hh)
+
+
+def _gru_setup(ctx, inputs, output):
+    x, weight_ih, weight_hh, seqlen = inputs
+    ctx.has_seqlen = seqlen is not None
+    ctx.save_for_backward(x, weight_ih, weight_hh, *([seqlen] if ctx.has_seqlen else []), output[0], output[1])
+    ctx.mark_non_differentiable(output[1])
+
+
+def _gru_backward(ctx, g_y, g_saved):
+    x, weight_ih, weight_hh, *rest = ctx.saved_tensors
+    seqlen = rest[0] if ctx.has_seqlen else None
+    y, saved = rest[-2:]
+    dx, dw_ih, dw_hh = gru_layer_backward(x, weight_ih, weight_hh, seqlen, y, saved, g_y)
+    return dx, dw_ih, dw_hh, None
+
+
+gru_layer.register_autograd(_gru_backward, setup_context=_gru_setup)
+
+
 OPS = ("embed_gather_posadd", "score_bce", "score_bce_backward", "score_bpr", "score_bpr_backward", "loss_from_scores",
        "loss_from_scores_backward", "neg_sample", "full_score_topk", "target_rank", "fused_adam_",
        "sasrec_layer", "sasrec_layer_backward", "seq_pool", "seq_pool_backward", "dropout", "embed_gather_posadd_backward",
-       "fmlp_layer", "fmlp_layer_backward", "layer_norm", "layer_norm_backward")
+       "fmlp_layer", "fmlp_layer_backward", "layer_norm", "layer_norm_backward", "gru_layer", "gru_layer_backward")

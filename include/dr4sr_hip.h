@@ -1009,6 +1009,39 @@ int dr4sr_layer_norm_fwd(const float* x, const float* weight, const float* bias,
 int dr4sr_layer_norm_bwd(const float* x, const float* weight, int64_t n_rows, int32_t D, float eps, const float* dy, float* dx, float* dw,
                          float* db, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- additive to ABI 10: the stateless GRU layer op on dense tensors (csrc/gru_op.hip; what torch.ops.dr4sr_hip.gru_layer runs).  No
+ * plan, no workspace that survives a call, no device state words, no communication between workgroups inside a launch.
+ *
+ * ONE layer of torch.nn.GRU(bias=False, batch_first=True) (module/layers.py:117-136) on x [B, L, I] fp32, contiguous, h_0 = 0;
+ * w_ih [3H, I] and w_hh [3H, H] hold the gates in torch's order r | z | n:
+ *     gi = x_t w_ih^T ;  gh = h_{t-1} w_hh^T
+ *     r = sigmoid(gi_r + gh_r) ;  z = sigmoid(gi_z + gh_z) ;  n = tanh(gi_n + r * gh_n) ;  h_t = (1 - z) * n + z * h_{t-1}
+ * y [B, L, H] holds every h_t.  fp32 MFMA throughout.
+ * Supported shapes (anything else: DR4SR_E_SHAPE, from the size entry points and from the calls, before any launch): I = 64, 128 or 256,
+ * H = 128 or 256, 1 <= L <= 1024.  DR4SR_E_ARG: a null pointer (seqlen may be NULL, and in the forward saved), B < 0 or above 2^24.  A
+ * null or too small workspace (dr4sr_gru_layer_workspace_bytes with backward = 0 for the forward, 1 for the backward): DR4SR_E_WS;
+ * nothing in it survives a call.  B = 0 launches nothing (the backward zero-fills dw_ih and dw_hh); the activation pointers and the
+ * workspace may then be null.  Index arithmetic is 64-bit.
+ *
+ * seqlen: NULL computes all L steps of every sequence, as the reference does (it feeds the pads).  With seqlen [B] (int64, on the
+ * device) every value is clamped to [0, L] and the steps at and behind seqlen[b] are skipped: y and dx are exactly 0 there, x and dy
+ * there are never read (they may hold anything).  Both agree wherever only positions in front of seqlen[b] are read downstream (the
+ * recurrence is causal; 'origin' and 'last' pooling read nothing else).  A sequence of length 0 is legal and gives zeros.
+ *
+ * saved (forward: written when non-NULL; backward: read) is opaque, dr4sr_gru_layer_saved_floats floats (r, z, n and gh_n per token;
+ * h_{t-1} is y shifted by one step): NULL for inference.  The backward takes the inputs and the y of the forward it differentiates; dx,
+ * dw_ih and dw_hh are WRITTEN, not accumulated.  It uses no float atomics: every workgroup of the weight-gradient launch sums the
+ * 64-token tiles of its token split in index order into its own slot of ws, a last launch adds the slots in index order — two calls
+ * give the same bits.  Launches on `stream` only (capturable), no allocation, no host synchronisation. */
+/* floats / bytes, or a negative DR4SR_E_* code */
+int64_t dr4sr_gru_layer_saved_floats(int64_t B, int32_t L, int32_t I, int32_t H);
+int64_t dr4sr_gru_layer_workspace_bytes(int64_t B, int32_t L, int32_t I, int32_t H, int32_t backward);
+int dr4sr_gru_layer_fwd(const float* x, const float* w_ih, const float* w_hh, const int64_t* seqlen, int64_t B, int32_t L, int32_t I,
+                        int32_t H, float* y, float* saved, void* ws, int64_t ws_bytes, void* stream);
+int dr4sr_gru_layer_bwd(const float* x, const float* w_ih, const float* w_hh, const int64_t* seqlen, int64_t B, int32_t L, int32_t I,
+                        int32_t H, const float* y, const float* saved, const float* dy, float* dx, float* dw_ih, float* dw_hh, void* ws,
+                        int64_t ws_bytes, void* stream);
+
 /* Test / measurement hooks (dr4sr_dropout_mask, dr4sr_*_launch_kernel) are NOT part of this product surface: they are declared in
  * include/dr4sr_hip_hooks.h, and nothing under dr4sr_amd/ calls them. */
 
