@@ -389,6 +389,15 @@ SYMBOLS = {
                                       C.c_int64, C.c_void_p]),
     "dr4sr_gru_layer_bwd": (C.c_int, [_f32p, _f32p, _f32p, _i64p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _f32p, _f32p, _f32p, _f32p,
                                       _f32p, _f32p, C.c_void_p, C.c_int64, C.c_void_p]),
+    # additive to ABI 10: the encoder-layer op with sequence lengths, short sequences sharing a tile (csrc/layer_packed.hip)
+    "dr4sr_sasrec_layer_packed_saved_floats": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "dr4sr_sasrec_layer_packed_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "dr4sr_sasrec_layer_packed_fwd": (C.c_int, [_f32p, _i64p, C.c_int32, C.POINTER(LayerWeights), C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                C.c_int32, C.c_float, C.c_float, C.c_uint64, C.c_uint32, C.c_int32, _f32p, _f32p, C.c_void_p,
+                                                C.c_int64, C.c_void_p]),
+    "dr4sr_sasrec_layer_packed_bwd": (C.c_int, [_f32p, _i64p, C.c_int32, C.POINTER(LayerWeights), C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                C.c_int32, C.c_float, C.c_float, C.c_uint64, C.c_uint32, C.c_int32, _f32p, _f32p, _f32p,
+                                                C.POINTER(LayerGrads), C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 _lib = None
@@ -405,7 +414,9 @@ _AFTER_PARENT_AB = ("dr4sr_sasrec_encode_w", "dr4sr_sasrec_encode_w_bwd", "dr4sr
                     "dr4sr_seq_pool_fwd", "dr4sr_seq_pool_bwd", "dr4sr_dropout_apply", "dr4sr_embed_gather_posadd_bwd",
                     "dr4sr_fmlp_layer_saved_floats", "dr4sr_fmlp_layer_workspace_bytes", "dr4sr_fmlp_layer_fwd", "dr4sr_fmlp_layer_bwd",
                     "dr4sr_layer_norm_workspace_bytes", "dr4sr_layer_norm_fwd", "dr4sr_layer_norm_bwd",
-                    "dr4sr_gru_layer_saved_floats", "dr4sr_gru_layer_workspace_bytes", "dr4sr_gru_layer_fwd", "dr4sr_gru_layer_bwd")
+                    "dr4sr_gru_layer_saved_floats", "dr4sr_gru_layer_workspace_bytes", "dr4sr_gru_layer_fwd", "dr4sr_gru_layer_bwd",
+                    "dr4sr_sasrec_layer_packed_saved_floats", "dr4sr_sasrec_layer_packed_workspace_bytes", "dr4sr_sasrec_layer_packed_fwd",
+                    "dr4sr_sasrec_layer_packed_bwd")
 
 
 def load():
@@ -444,6 +455,10 @@ def load():
 LANE_PROBE_NAMES = ("group16_sum", "group8_sum", "wave_sum", "xg_max", "xg_sum", "fold", "xor1")      # DR4SR_LP_*
 PROBE_SYMBOLS = {
     "dr4sr_lane_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    # the tile plan of the packed encoder-layer op on its own (csrc/layer_packed.hip)
+    "dr4sr_sasrec_layer_packed_chunk": (C.c_int32, []),
+    "dr4sr_sasrec_layer_packed_plan": (C.c_int, [_i64p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                 C.c_void_p]),
 }
 
 

@@ -19,22 +19,10 @@
 // backward, the row passes and the slot reduction are op_tiles.h's (shared with fmlp_op.hip).
 #include "common.h"
 #include "op_tiles.h"
+#include "layer_geo.h"
 
 namespace lop {
 using namespace optile;
-
-constexpr int LDT = 68;                // row stride of the [64][64] attention tiles
-constexpr int TILE = 64 * LDT;
-
-template <int D, int F> struct Geo {
-    static constexpr int LDX = D + 4, LDF = F + 4, DH = D / 2, HG = 64 / DH, NG = D / 64;
-    static constexpr int R_FLOATS = (64 * LDF > (3 + 2 * HG) * TILE) ? 64 * LDF : (3 + 2 * HG) * TILE;
-    static constexpr int LDS_FLOATS = 2 * 64 * LDX + R_FLOATS + 64 + 4 * 64;
-    // one slot of weight-gradient partials: the 12 tensors in the flat layout's order
-    static constexpr int O_INW = 0, O_INB = O_INW + 3 * D * D, O_OW = O_INB + 3 * D, O_OB = O_OW + D * D, O_W1 = O_OB + D, O_B1 = O_W1 + F * D,
-                         O_W2 = O_B1 + F, O_B2 = O_W2 + D * F, O_N1W = O_B2 + D, O_N1B = O_N1W + D, O_N2W = O_N1B + D, O_N2B = O_N2W + D,
-                         NW = O_N2B + D;
-};
 
 __host__ __device__ inline int64_t saved_stride(int L, int D, int F) { return (((int64_t)L * (6 * D + F) + 2 * (int64_t)L * L) + 3) & ~(int64_t)3; }
 
@@ -356,16 +344,6 @@ __global__ void k_embed_bwd_pos(const float* __restrict__ dx, int B, int LD, flo
 }
 
 // =================================================================================================================== host
-static int shape_check(int64_t B, int L, int D, int H, int F) {
-    if (B < 0 || L < 1 || D < 1 || H < 1 || F < 1) return DR4SR_E_ARG;
-    if (L > 64 || D % H) return DR4SR_E_SHAPE;
-    const int dh = D / H;
-    if (!((D == 64 && (F == 128 || F == 256) && dh == 32) || (D == 128 && F == 128 && dh == 64))) return DR4SR_E_SHAPE;
-    if (B * (int64_t)L * L >= ((int64_t)1 << 30)) return DR4SR_E_ARG;      // 32-bit sequence x head index of the attention dropout stream
-    return 0;
-}
-static int64_t slot_floats(int D, int F) { return 4 * (int64_t)D * D + 2 * (int64_t)D * F + 9 * (int64_t)D + F; }
-
 template <int D, int F>
 static int launch_fwd(const Args& a, hipStream_t st) {
     const size_t lds = Geo<D, F>::LDS_FLOATS * sizeof(float);

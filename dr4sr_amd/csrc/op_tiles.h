@@ -302,6 +302,189 @@ __device__ __forceinline__ void ffn_ln_bwd(float* As, float* Bs, int ldx, float*
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------ row-indirect variants
+// The same passes for a tile whose rows are tokens of SEVERAL sequences (layer_packed.hip): tok (LDS, 64 ints) is the row table, tok[row] =
+// b * L + pos of the token in row < n, n the tile's fill; rows behind n are zero.  Global [B L][ldg] tensors are addressed by tok[row] where
+// the passes above use t0 + row, and so is every dropout element: a token draws what it draws in a tile of its own.
+template <int W>
+__device__ __forceinline__ void load_rows_ix(float* __restrict__ dst, int ld, const float* __restrict__ src, int ldg, const int* __restrict__ tok,
+                                             int n) {
+    constexpr int C4 = W / 4;
+    for (int i = threadIdx.x; i < 64 * C4; i += 256) {
+        const int row = i / C4, c = (i % C4) * 4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row < n) v = ld4(src + (size_t)tok[row] * ldg + c);
+        st4(dst + row * ld + c, v);
+    }
+}
+// LDS [64][ld] rows [0, n), W columns -> global [B L][ldg] (dst points at the first column)
+template <int W>
+__device__ __forceinline__ void store_rows_ix(float* __restrict__ dst, int ldg, const float* __restrict__ src, int ld, const int* __restrict__ tok,
+                                              int n) {
+    constexpr int C4 = W / 4;
+    for (int i = threadIdx.x; i < n * C4; i += 256) {
+        const int row = i / C4, c = (i % C4) * 4;
+        st4(dst + (size_t)tok[row] * ldg + c, ld4(src + row * ld + c));
+    }
+}
+// res_drop_ln_rows; sv_u is global [B L][D]; dst is an LDS tile of row stride ldd, or with GLOBAL_DST global [B L][D]
+template <int D, bool GLOBAL_DST>
+__device__ __forceinline__ void res_drop_ln_rows_ix(float* dst, int ldd, const float* res, const float* o, int ld, const float* gam,
+                                                    const float* bet, float* sv_u, const RngKey& rk, bool drop, uint32_t site,
+                                                    const int* tok, int n, float eps) {
+    constexpr int NV = D / 64;
+    for (int row = threadIdx.x >> 4; row < n; row += 16) {
+        const int j16 = threadIdx.x & 15;
+        const uint64_t t = (uint64_t)tok[row];
+        float4 u[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = 4 * j16 + 64 * j;
+            float4 ov = ld4(o + row * ld + c);
+            if (drop) ov = mul4(ov, drop4(rk, site, t * D + c));
+            u[j] = add4(ld4(res + row * ld + c), ov);
+            if (sv_u) st4(sv_u + t * D + c, u[j]);
+        }
+        float mean, rstd;
+        ln_stats16<NV>(u, mean, rstd, eps);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = 4 * j16 + 64 * j;
+            float* d = GLOBAL_DST ? dst + t * D + c : dst + (size_t)row * ldd + c;
+            st4(d, ln_apply(u[j], mean, rstd, ld4(gam + c), ld4(bet + c)));
+        }
+    }
+}
+// ln_bwd_rows; dres is global [B L][D] or null
+template <int D>
+__device__ __forceinline__ void ln_bwd_rows_ix(float* dZ, float* U, int ld, const float* st, const float* gam, float* dres,
+                                               const RngKey& rk, bool drop, uint32_t site, const int* tok, int n) {
+    constexpr int NV = D / 64;
+    for (int row = threadIdx.x >> 4; row < 64; row += 16) {
+        const int j16 = threadIdx.x & 15;
+        const uint64_t t = row < n ? (uint64_t)tok[row] : 0;
+        float4 dz[NV], u[NV], gm[NV], dg[NV], db[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = 4 * j16 + 64 * j;
+            dz[j] = ld4(dZ + row * ld + c); u[j] = ld4(U + row * ld + c); gm[j] = ld4(gam + c);
+            dg[j] = db[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        ln_bwd_row<NV>(dz, u, st[2 * row], st[2 * row + 1], gm, dg, db);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = 4 * j16 + 64 * j;
+            st4(dZ + row * ld + c, dz[j]);
+            if (dres && row < n) st4(dres + t * D + c, dz[j]);
+            float4 dv = dz[j];
+            if (drop && row < n) dv = mul4(dv, drop4(rk, site, t * D + c));
+            st4(U + row * ld + c, dv);
+        }
+    }
+}
+// ln_recompute_rows; sv_u is global [B L][D]
+template <int D>
+__device__ __forceinline__ void ln_recompute_rows_ix(float* dst, int ld, const float* sv_u, float* st, const float* gam, const float* bet,
+                                                     const int* tok, int n, float eps) {
+    constexpr int NV = D / 64;
+    for (int row = threadIdx.x >> 4; row < 64; row += 16) {
+        const int j16 = threadIdx.x & 15;
+        float4 u[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) u[j] = row < n ? ld4(sv_u + (size_t)tok[row] * D + 4 * j16 + 64 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
+        float mean, rstd;
+        ln_stats16<NV>(u, mean, rstd, eps);
+        if (j16 == 0) { st[2 * row] = row < n ? mean : 0.f; st[2 * row + 1] = row < n ? rstd : 0.f; }
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = 4 * j16 + 64 * j;
+            float4 yv = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (row < n) yv = ln_apply(u[j], mean, rstd, ld4(gam + c), ld4(bet + c));
+            st4(dst + row * ld + c, yv);
+        }
+    }
+}
+// gelu_sweep; src is the LDS tile itself (row stride lds_), or with GLOBAL_SRC the saved pre-activation, global [B L][F]; save is
+// global [B L][F] or null
+template <int F, bool GRAD, bool ACT_DROP, bool GLOBAL_SRC>
+__device__ __forceinline__ void gelu_sweep_ix(float* dst, int ldd, const float* src, int lds_, float* save, const RngKey& rk, bool drop,
+                                              uint32_t site, const int* tok, int n) {
+    for (int i = threadIdx.x; i < 64 * (F / 4); i += 256) {
+        const int row = i / (F / 4), c = (i % (F / 4)) * 4;
+        float4 hv = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row < n) {
+            const uint64_t t = (uint64_t)tok[row];
+            hv = ld4(GLOBAL_SRC ? src + t * F + c : src + (size_t)row * lds_ + c);
+            if (save) st4(save + t * F + c, hv);
+            hv = GRAD ? make_float4(gelu_erf_grad(hv.x), gelu_erf_grad(hv.y), gelu_erf_grad(hv.z), gelu_erf_grad(hv.w))
+                      : make_float4(gelu_erf(hv.x), gelu_erf(hv.y), gelu_erf(hv.z), gelu_erf(hv.w));
+            if (ACT_DROP && drop) hv = mul4(hv, drop4(rk, site, t * F + c));
+        }
+        st4(dst + row * ldd + c, hv);
+    }
+}
+// ffn_fwd; y, sv_h and sv_u2 are the whole global tensors ([B L][D], [B L][F], [B L][D])
+template <int D, int F, bool ACT_DROP>
+__device__ __forceinline__ void ffn_fwd_ix(float* As, float* Bs, int ldx, float* R, int ldf, const FfnWeights& w, float* sv_h, float* sv_u2,
+                                           float* y, const RngKey& rk, bool drop, uint32_t s_act, uint32_t s_ffn, const int* tok, int n,
+                                           float eps) {
+    {
+        f32x16 acc[F / 64];
+        acc_zero(acc);
+        mma_64xN<D, F / 64>(As, ldx, w.w1, acc);
+        acc_to_lds<F / 64>(acc, R, ldf, w.b1);
+    }
+    __syncthreads();
+    gelu_sweep_ix<F, false, ACT_DROP, false>(R, ldf, R, ldf, sv_h, rk, drop, s_act, tok, n);
+    __syncthreads();
+    {
+        f32x16 acc[D / 64];
+        acc_zero(acc);
+        mma_64xN<F, D / 64>(R, ldf, w.w2, acc);
+        acc_to_lds<D / 64>(acc, Bs, ldx, w.b2);
+    }
+    __syncthreads();
+    res_drop_ln_rows_ix<D, true>(y, D, As, Bs, ldx, w.ln_w, w.ln_b, sv_u2, rk, drop, s_ffn, tok, n, eps);
+}
+// ffn_ln_bwd; dy, u_in, sv_h and sv_u2 are the whole global tensors
+template <int D, int F, bool ACT_DROP>
+__device__ __forceinline__ void ffn_ln_bwd_ix(float* As, float* Bs, int ldx, float* R, int ldf, float* st1, float* st2, const FfnWeights& w,
+                                              const float* u_in, const float* sv_h, const float* sv_u2, const float* dy, const FfnGrads& g,
+                                              const RngKey& rk, bool drop, uint32_t s_act, uint32_t s_ffn, const int* tok, int n, float eps,
+                                              bool first) {
+    load_rows_ix<D>(As, ldx, dy, D, tok, n);
+    load_rows_ix<D>(Bs, ldx, sv_u2, D, tok, n);
+    __syncthreads();
+    ln_stats_rows<D>(Bs, ldx, st2, n, eps);
+    __syncthreads();
+    ln_affine_grads<D>(g.ln_w, g.ln_b, As, Bs, ldx, st2, n, first);
+    __syncthreads();
+    ln_bwd_rows_ix<D>(As, Bs, ldx, st2, w.ln_w, nullptr, rk, drop, s_ffn, tok, n);                      // du2 -> As, d f2 = du2 * mask -> Bs
+    gelu_sweep_ix<F, false, ACT_DROP, true>(R, ldf, sv_h, F, nullptr, rk, drop, s_act, tok, n);         // hd = drop(gelu(hpre)) -> R
+    __syncthreads();
+    wgrad_tn<D, F>(g.w2, F, Bs, ldx, R, ldf, first);
+    colsum(g.b2, Bs, ldx, D, n, first);
+    __syncthreads();
+    gelu_sweep_ix<F, true, ACT_DROP, true>(R, ldf, sv_h, F, nullptr, rk, drop, s_act, tok, n);
+    {
+        f32x16 acc[F / 64];
+        acc_zero(acc);
+        mma_wT<D, F / 64>(Bs, ldx, w.w2, F, acc);
+        __syncthreads();                                       // the factor is in R, every wave is done reading d f2 from Bs
+        acc_each(acc, [=](int row, int col, float v) { float* pp = R + row * ldf + col; *pp *= v; });
+    }
+    ln_recompute_rows_ix<D>(Bs, ldx, u_in, st1, w.ln0_w, w.ln0_b, tok, n, eps);                         // x1 -> Bs, statistics -> st1
+    __syncthreads();
+    wgrad_tn<F, D>(g.w1, D, R, ldf, Bs, ldx, first);
+    colsum(g.b1, R, ldf, F, n, first);
+    {
+        f32x16 acc[D / 64];
+        acc_zero(acc);
+        mma_wT<F, D / 64>(R, ldf, w.w1, D, acc);
+        acc_each(acc, [=](int row, int col, float v) { float* pp = As + row * ldx + col; *pp += v; });   // d x1 = d hpre W1 + du2
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------ slot reduction
 // Element e of a slot belongs to the first destination whose end lies behind it; a destination begins where the one before it ends
 // (the first at `begin`).  Unused entries end where the last used one does, so end[REDUCE_MAX - 1] is the slot's end.

@@ -13,6 +13,16 @@ training forward uses self.step and then advances it by one, so two forwards nev
 step).  A query position with no admissible key (a padded row on the id path) gets a zero attention context where torch yields NaN; the
 reference never reads such a position.
 
+use_seqlen=True (default False: the path above, bit for bit) runs the layers of the id path as torch.ops.dr4sr_hip.sasrec_layer_packed
+(csrc/layer_packed.hip) on batch['seqlen']: short sequences share a 64-row tile, so the work goes with the valid tokens, and the rows at
+and behind each length come out as zeros instead of the dense op's values there.  Nothing that the poolings read changes (the dropout
+masks are the same).  ONE requirement: the ids are non-zero exactly at pos < seqlen — post-padded rows, which is what the project's and
+the reference's SASRec datasets deliver.  The module checks it per batch, one device reduction and one host read beside the id check
+embed_gather_posadd already makes, and under the same two exemptions (inside a stream capture, under DR4SR_NO_ID_CHECK), where it is
+the caller's to keep.  A batch that does not meet it (an id 0 in front of a length: the reference masks that key, sasrec_layer_packed
+has no way to) runs the dense op: the flag never changes what the module computes, only how.  The `seq_emb` path keeps the dense op
+whatever the flag says.
+
 FMLPEncoderOps / FMLPOps — the reference's FMLPEncoder (module/layers.py:740-808) and the encoder half of its FMLP model (model/fmlp.py:8-39)
 written the same way: each `Layer` (FilterLayer + Intermediate) is one torch.ops.dr4sr_hip.fmlp_layer (csrc/fmlp_op.hip), the embedding
 LayerNorm torch.ops.dr4sr_hip.layer_norm.  Parameters carry the reference's names, so a checkpoint of the engine-backed FMLP loads with
@@ -27,6 +37,7 @@ behind the GRU is the reference's own nn.Linear outside GRULayer and stays torch
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -82,7 +93,8 @@ class _Stack(nn.Module):
 
 class SASRecQueryEncoderOps(nn.Module):
     def __init__(self, fiid, embed_dim, max_seq_len, n_head, hidden_size, dropout, activation, layer_norm_eps, n_layer, item_encoder,
-                 bidirectional=False, training_pooling_type="origin", eval_pooling_type="last", seed: int = 2023) -> None:
+                 bidirectional=False, training_pooling_type="origin", eval_pooling_type="last", seed: int = 2023,
+                 use_seqlen: bool = False) -> None:
         super().__init__()
         if activation != "gelu":
             raise NotImplementedError("torch.ops.dr4sr_hip.sasrec_layer computes the exact-erf GELU only (activation='gelu')")
@@ -97,10 +109,24 @@ class SASRecQueryEncoderOps(nn.Module):
         self.position_emb = nn.Embedding(max_seq_len, embed_dim)
         self.transformer_layer = _Stack(embed_dim, hidden_size, n_layer)
         self.seed, self.step = int(seed), 0
+        self.use_seqlen = bool(use_seqlen)
+
+    @staticmethod
+    def _post_padded(idx, seqlen):
+        """are the ids non-zero exactly at pos < seqlen?  (what sasrec_layer_packed's key mask assumes; not looked at where
+        embed_gather_posadd does not look at the ids either)"""
+        if torch.cuda.is_current_stream_capturing() or os.environ.get("DR4SR_NO_ID_CHECK"):
+            return True
+        L = idx.shape[1]
+        valid = torch.arange(L, device=idx.device).view(1, L) < seqlen.clamp(0, L).view(-1, 1)
+        return bool(((idx != 0) == valid).all())
 
     def forward(self, batch, need_pooling=True):
         o = torch.ops.dr4sr_hip
         p = self.p_drop if self.training else 0.0
+        packed = self.use_seqlen and batch.get("seq_emb", None) is None      # seq_emb: no padding mask, every position is a key
+        if packed:
+            packed = self._post_padded(batch["in_" + self.fiid], batch["seqlen"])
         seed, step = self.seed, self.step
         if batch.get("seq_emb", None) is None:                                  # sasrec.py:42-48
             idx = batch["in_" + self.fiid]
@@ -116,7 +142,11 @@ class SASRecQueryEncoderOps(nn.Module):
         if p > 0.0:                                                             # sasrec.py:66
             x = o.dropout(x, p, seed, step, _lib.SITE_EMB)
         for i, layer in enumerate(self.transformer_layer.layers):               # sasrec.py:65-68
-            x, _ = o.sasrec_layer(x, key_pad, not self.bidirectional, *layer.tensors(), self.n_head, self.eps, p, seed, step, i)
+            if packed:
+                x, _ = o.sasrec_layer_packed(x.contiguous(), batch["seqlen"], not self.bidirectional, *layer.tensors(), self.n_head,
+                                             self.eps, p, seed, step, i)
+            else:
+                x, _ = o.sasrec_layer(x, key_pad, not self.bidirectional, *layer.tensors(), self.n_head, self.eps, p, seed, step, i)
         if self.training:
             self.step += 1
         if not need_pooling:

@@ -17,6 +17,9 @@ a reference-style model written against plain torch ops:
     sasrec_layer(x, key_padding_mask?, causal, <12 layer tensors>, n_head, eps, p_drop, seed, step, layer) -> (y, saved)
                                                               one TransformerEncoderLayer of model/sasrec.py:21-30,:68 on dense [B, L, D]
                                                               (autograd: d x and the 12 weight gradients, bit-reproducible)
+    sasrec_layer_packed(x, seqlen, causal, <12 layer tensors>, n_head, eps, p_drop, seed, step, layer) -> (y, saved)
+                                                              the same layer on post-padded rows: keys at pos >= seqlen[b] are padded, y is
+                                                              0 there; short sequences share a 64-row tile (csrc/layer_packed.hip)
     seq_pool(x, seqlen, pooling) -> out                       module/layers.py:41-73 'origin' | 'last', module/functional.py:50-55 'mean'
     dropout(x, p_drop, seed, step, site) -> out               model/sasrec.py:66 with the library's Philox masks (DR4SR_SITE_EMB)
     fmlp_layer(x, complex_weight, filter_ln_w, filter_ln_b, dense_1_w, dense_1_b, dense_2_w, dense_2_b, inter_ln_w, inter_ln_b,
@@ -26,7 +29,7 @@ a reference-style model written against plain torch ops:
     gru_layer(x, weight_ih, weight_hh, seqlen?) -> (y, saved)   one layer of nn.GRU(bias=False, batch_first=True), module/layers.py:117-136, on
                                                               dense [B, L, I]; seqlen skips the steps behind each length (autograd: d x,
                                                               d weight_ih, d weight_hh, bit-reproducible)
-    (+ embed_gather_posadd_backward, sasrec_layer_backward, seq_pool_backward, fmlp_layer_backward, layer_norm_backward,
+    (+ embed_gather_posadd_backward, sasrec_layer_backward, sasrec_layer_packed_backward, seq_pool_backward, fmlp_layer_backward, layer_norm_backward,
      gru_layer_backward: the autograd formulas, ops themselves)
 
 Every implementation only enqueues HIP kernels of libdr4sr_hip.so on the current stream; there is no CPU kernel (the ops raise on
@@ -409,6 +412,118 @@ def _layer_backward(ctx, g_y, g_saved):
 sasrec_layer.register_autograd(_layer_backward, setup_context=_layer_setup)
 
 
+# ------------------------------------------------------------------------------------------------ encoder layer with sequence lengths
+_W_NAMES = ("in_proj_weight", "in_proj_bias", "out_proj_weight", "out_proj_bias", "linear1_weight", "linear1_bias", "linear2_weight",
+            "linear2_bias", "norm1_weight", "norm1_bias", "norm2_weight", "norm2_bias")
+
+
+def _packed_saved_floats(B, L, D, F):
+    return B * (L * (6 * D + F) + 2 * L * L)                         # dr4sr_sasrec_layer_packed_saved_floats for a supported shape
+
+
+def _packed_args(what, x, seqlen, ws_, n_head, backward, extra=()):
+    """(B, L, D, H, F, saved floats, workspace bytes) of a sasrec_layer_packed call; every refusal (device, dtype, contiguity, shape) is
+    raised here, before a launch.  Nothing is converted or copied: the op takes the tensors as they are or not at all"""
+    named = (("x", x),) + tuple(zip(_W_NAMES, ws_)) + tuple(extra)
+    _need_cuda(seqlen, *[t for _, t in named])
+    for name, t in named:
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device:
+            raise _lib.Dr4srError(f"{what}: {name} must be a contiguous float32 tensor on x's device")
+    if x.dim() != 3:
+        raise _lib.Dr4srError(f"{what}: x must be [B, L, D]")
+    B, L, D = (int(v) for v in x.shape)
+    if seqlen.dtype != torch.int64 or seqlen.dim() != 1 or seqlen.shape[0] != B or not seqlen.is_contiguous() or seqlen.device != x.device:
+        raise _lib.Dr4srError(f"{what}: seqlen must be a contiguous int64 tensor [B] = [{B}] on x's device")
+    H, F = int(n_head), int(ws_[4].shape[0]) if ws_[4].dim() == 2 else 0
+    shapes = ((3 * D, D), (3 * D,), (D, D), (D,), (F, D), (F,), (D, F), (D,), (D,), (D,), (D,), (D,))
+    for name, t, shp in zip(_W_NAMES, ws_, shapes):
+        if tuple(t.shape) != shp:
+            raise _lib.Dr4srError(f"{what}: {name} must be {shp} for x [B, L, {D}], got {tuple(t.shape)}")
+    lib = _lib.load()
+    n = int(lib.dr4sr_sasrec_layer_packed_saved_floats(B, L, D, H, F))          # the shape refusals (DR4SR_E_SHAPE)
+    _lib.check(min(n, 0), "dr4sr_sasrec_layer_packed_saved_floats")
+    nb = int(lib.dr4sr_sasrec_layer_packed_workspace_bytes(B, L, D, H, F, backward))
+    _lib.check(min(nb, 0), "dr4sr_sasrec_layer_packed_workspace_bytes")
+    return B, L, D, H, F, n, nb
+
+
+@torch.library.custom_op(f"{NS}::sasrec_layer_packed", mutates_args=())
+def sasrec_layer_packed(x: torch.Tensor, seqlen: torch.Tensor, causal: bool, in_proj_weight: torch.Tensor, in_proj_bias: torch.Tensor,
+                        out_proj_weight: torch.Tensor, out_proj_bias: torch.Tensor, linear1_weight: torch.Tensor,
+                        linear1_bias: torch.Tensor, linear2_weight: torch.Tensor, linear2_bias: torch.Tensor, norm1_weight: torch.Tensor,
+                        norm1_bias: torch.Tensor, norm2_weight: torch.Tensor, norm2_bias: torch.Tensor, n_head: int, eps: float,
+                        p_drop: float, seed: int, step: int, layer: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """sasrec_layer on post-padded rows: sequence b has clamp(seqlen[b], 0, L) valid positions from 0, its keys behind them are padded;
+    y is exactly 0 there and x there is never read.  Short sequences share a 64-row tile (csrc/layer_packed.hip); the dropout masks are
+    sasrec_layer's.  `saved` is the opaque buffer the backward reads"""
+    ws_ = (in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, linear1_weight, linear1_bias, linear2_weight, linear2_bias,
+           norm1_weight, norm1_bias, norm2_weight, norm2_bias)
+    B, L, D, H, F, n, nb = _packed_args("sasrec_layer_packed", x, seqlen, ws_, n_head, 0)
+    lib = _lib.load()
+    y = torch.empty_like(x)
+    saved = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(nb // 4, 1), dtype=torch.int32, device=x.device)
+    w = _layer_struct(_lib.LayerWeights, ws_)
+    _lib.check(lib.dr4sr_sasrec_layer_packed_fwd(_lib.ptr(x), _lib.ptr(seqlen), int(causal), w, B, L, D, H, F, eps, p_drop,
+                                                 seed & 0xFFFFFFFFFFFFFFFF, step & 0xFFFFFFFF, layer, _lib.ptr(y), _lib.ptr(saved),
+                                                 _lib.ptr(ws), nb, _lib.cur_stream()), "dr4sr_sasrec_layer_packed_fwd")
+    return y, saved
+
+
+@sasrec_layer_packed.register_fake
+def _(x, seqlen, causal, in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, linear1_weight, linear1_bias, linear2_weight,
+      linear2_bias, norm1_weight, norm1_bias, norm2_weight, norm2_bias, n_head, eps, p_drop, seed, step, layer):
+    B, L, D = x.shape
+    return torch.empty_like(x), x.new_empty(max(_packed_saved_floats(B, L, D, linear1_weight.shape[0]), 1))
+
+
+@torch.library.custom_op(f"{NS}::sasrec_layer_packed_backward", mutates_args=())
+def sasrec_layer_packed_backward(x: torch.Tensor, seqlen: torch.Tensor, causal: bool, in_proj_weight: torch.Tensor,
+                                 in_proj_bias: torch.Tensor, out_proj_weight: torch.Tensor, out_proj_bias: torch.Tensor,
+                                 linear1_weight: torch.Tensor, linear1_bias: torch.Tensor, linear2_weight: torch.Tensor,
+                                 linear2_bias: torch.Tensor, norm1_weight: torch.Tensor, norm1_bias: torch.Tensor,
+                                 norm2_weight: torch.Tensor, norm2_bias: torch.Tensor, n_head: int, eps: float, p_drop: float, seed: int,
+                                 step: int, layer: int, saved: torch.Tensor, dy: torch.Tensor) -> List[torch.Tensor]:
+    """-> [dx, the 12 weight gradients in the argument order]; written, not accumulated; bit-reproducible.  dx is exactly 0 at and
+    behind each length, dy there is never read"""
+    ws_ = (in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, linear1_weight, linear1_bias, linear2_weight, linear2_bias,
+           norm1_weight, norm1_bias, norm2_weight, norm2_bias)
+    B, L, D, H, F, n, nb = _packed_args("sasrec_layer_packed_backward", x, seqlen, ws_, n_head, 1, (("saved", saved), ("dy", dy)))
+    if dy.shape != x.shape or saved.numel() < n:
+        raise _lib.Dr4srError("sasrec_layer_packed_backward: dy must be [B, L, D], saved the forward's")
+    lib = _lib.load()
+    dx = torch.empty_like(x)
+    dws = [torch.empty_like(t) for t in ws_]
+    ws = torch.empty(max(nb // 4, 1), dtype=torch.int32, device=x.device)
+    w, g = _layer_struct(_lib.LayerWeights, ws_), _layer_struct(_lib.LayerGrads, dws)
+    _lib.check(lib.dr4sr_sasrec_layer_packed_bwd(_lib.ptr(x), _lib.ptr(seqlen), int(causal), w, B, L, D, H, F, eps, p_drop,
+                                                 seed & 0xFFFFFFFFFFFFFFFF, step & 0xFFFFFFFF, layer, _lib.ptr(saved), _lib.ptr(dy),
+                                                 _lib.ptr(dx), g, _lib.ptr(ws), nb, _lib.cur_stream()), "dr4sr_sasrec_layer_packed_bwd")
+    return [dx] + dws
+
+
+@sasrec_layer_packed_backward.register_fake
+def _(x, seqlen, causal, in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, linear1_weight, linear1_bias, linear2_weight,
+      linear2_bias, norm1_weight, norm1_bias, norm2_weight, norm2_bias, n_head, eps, p_drop, seed, step, layer, saved, dy):
+    return [torch.empty_like(t) for t in (x, in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, linear1_weight, linear1_bias,
+                                          linear2_weight, linear2_bias, norm1_weight, norm1_bias, norm2_weight, norm2_bias)]
+
+
+def _packed_setup(ctx, inputs, output):
+    ctx.rest = inputs[2:3] + inputs[15:]                    # causal, n_head, eps, p_drop, seed, step, layer
+    ctx.save_for_backward(*inputs[:2], *inputs[3:15], output[1])
+    ctx.mark_non_differentiable(output[1])
+
+
+def _packed_backward(ctx, g_y, g_saved):
+    x, seqlen, *w, saved = ctx.saved_tensors
+    out = sasrec_layer_packed_backward(x, seqlen, ctx.rest[0], *w, *ctx.rest[1:], saved, g_y.contiguous())
+    return (out[0], None, None, *out[1:], None, None, None, None, None, None)
+
+
+sasrec_layer_packed.register_autograd(_packed_backward, setup_context=_packed_setup)
+
+
 def _pool_shape(x, pooling):
     return x.shape if pooling == _lib.POOL_ORIGIN else (x.shape[0], x.shape[2])
 
@@ -737,5 +852,6 @@ gru_layer.register_autograd(_gru_backward, setup_context=_gru_setup)
 
 OPS = ("embed_gather_posadd", "score_bce", "score_bce_backward", "score_bpr", "score_bpr_backward", "loss_from_scores",
        "loss_from_scores_backward", "neg_sample", "full_score_topk", "target_rank", "fused_adam_",
-       "sasrec_layer", "sasrec_layer_backward", "seq_pool", "seq_pool_backward", "dropout", "embed_gather_posadd_backward",
+       "sasrec_layer", "sasrec_layer_backward", "sasrec_layer_packed", "sasrec_layer_packed_backward", "seq_pool", "seq_pool_backward",
+       "dropout", "embed_gather_posadd_backward",
        "fmlp_layer", "fmlp_layer_backward", "layer_norm", "layer_norm_backward", "gru_layer", "gru_layer_backward")

@@ -1042,6 +1042,39 @@ int dr4sr_gru_layer_bwd(const float* x, const float* w_ih, const float* w_hh, co
                         int32_t H, const float* y, const float* saved, const float* dy, float* dx, float* dw_ih, float* dw_hh, void* ws,
                         int64_t ws_bytes, void* stream);
 
+/* ---- additive to ABI 10: the encoder-layer op with sequence lengths, short sequences sharing a 64-row tile (csrc/layer_packed.hip; what
+ * torch.ops.dr4sr_hip.sasrec_layer_packed runs).  No plan that survives a call, no device state words, no host synchronisation.
+ *
+ * The layer, the supported shapes, the dropout sites and elements and the refusals are those of dr4sr_sasrec_layer_fwd / _bwd above; x, y,
+ * dy, dx are the same dense [B, L, D] fp32 tensors.  Instead of a key-padding mask the call takes seqlen [B] (int64, on the device; NULL:
+ * DR4SR_E_ARG): sequence b has n_b = clamp(seqlen[b], 0, L) valid positions 0 .. n_b - 1 (the rows are post-padded) and its keys at
+ * pos >= n_b are padded; causal != 0 adds triu(1).  y and dx are EXACTLY 0 at pos >= n_b; x and dy there are never read (they may hold
+ * anything).  At pos < n_b the result is that of the dense op with key_pad = (pos >= n_b) up to the summation order of the weight
+ * gradients, and the dropout decisions are the dense op's: an element's index uses the token's own (b, pos), so a sequence draws the same
+ * masks packed, dense, alone or in a batch.
+ *
+ * Work: a small launch on `stream` assigns the sequences to 64-row tiles, in chunks of C consecutive sequences planned independently
+ * (C: the probe dr4sr_sasrec_layer_packed_chunk, include/dr4sr_hip_probes.h).  A chunk starts a tile; a sequence with n_b = 0 takes no
+ * rows; a sequence that does not fit behind the rows already in the tile starts the next one; no sequence straddles a tile.  One
+ * workgroup computes one tile at a time, attention being
+ * block-diagonal over the tile's sequences.  The grid depends on B alone; the tile count stays on the device.
+ *
+ * saved is opaque, dr4sr_sasrec_layer_packed_saved_floats floats (never more than dr4sr_sasrec_layer_saved_floats of the shape); nothing
+ * is written into it for pos >= n_b; NULL for inference.  ws: dr4sr_sasrec_layer_packed_workspace_bytes (backward = 0 for the forward,
+ * 1 for the backward), else DR4SR_E_WS; nothing in it survives a call, the backward plans again from seqlen.  dx and the 12 tensors of dw
+ * are WRITTEN, not accumulated, without float atomics: a workgroup sums the tiles it owns (blockIdx.x, + gridDim.x, ...) in that order into
+ * its slot of ws, a last launch adds the min(tiles, slots) written slots in index order — two calls give the same bits.  B = 0 launches
+ * nothing and every n_b = 0 gives y = 0, dx = 0; in both cases the backward zero-fills dw. */
+int64_t dr4sr_sasrec_layer_packed_saved_floats(int64_t B, int32_t L, int32_t D, int32_t H, int32_t F);
+int64_t dr4sr_sasrec_layer_packed_workspace_bytes(int64_t B, int32_t L, int32_t D, int32_t H, int32_t F, int32_t backward);
+int dr4sr_sasrec_layer_packed_fwd(const float* x, const int64_t* seqlen, int32_t causal, const dr4sr_layer_weights* w, int64_t B, int32_t L,
+                                  int32_t D, int32_t H, int32_t F, float eps, float p_drop, uint64_t seed, uint32_t step, int32_t layer,
+                                  float* y, float* saved, void* ws, int64_t ws_bytes, void* stream);
+int dr4sr_sasrec_layer_packed_bwd(const float* x, const int64_t* seqlen, int32_t causal, const dr4sr_layer_weights* w, int64_t B, int32_t L,
+                                  int32_t D, int32_t H, int32_t F, float eps, float p_drop, uint64_t seed, uint32_t step, int32_t layer,
+                                  const float* saved, const float* dy, float* dx, const dr4sr_layer_grads* dw, void* ws, int64_t ws_bytes,
+                                  void* stream);
+
 /* Test / measurement hooks (dr4sr_dropout_mask, dr4sr_*_launch_kernel) are NOT part of this product surface: they are declared in
  * include/dr4sr_hip_hooks.h, and nothing under dr4sr_amd/ calls them. */
 

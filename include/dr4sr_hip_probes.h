@@ -25,6 +25,14 @@ extern "C" {
 #define DR4SR_LANE_PROBE_N   7
 int dr4sr_lane_probe(const float* in, const uint32_t* in_u, uint32_t* out, int64_t n, void* stream);
 
+/* The tile plan of dr4sr_sasrec_layer_packed_fwd / _bwd (csrc/layer_packed.hip) on its own.  _chunk: the number C of consecutive
+ * sequences that are planned together.  _plan: runs the plan launches for seqlen [B] (int64, device) on `stream` and writes, for every
+ * sequence, tile_of[b] (int32 [B], device; -1: n_b = 0, the sequence has no rows) and row_of[b] (int32 [B]: its first row in that tile,
+ * -1 beside tile_of = -1), and the tile count to n_tiles (int32 [1]).  ws as for the forward (backward = 0).  Refusals as the forward's. */
+int32_t dr4sr_sasrec_layer_packed_chunk(void);
+int dr4sr_sasrec_layer_packed_plan(const int64_t* seqlen, int64_t B, int32_t L, int32_t* tile_of, int32_t* row_of, int32_t* n_tiles, void* ws,
+                                   int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
